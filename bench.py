@@ -3,7 +3,13 @@
 step on N GPUs of one node (BASELINE.json metric: img/s whole node at
 total batch 256 == 32/GPU x 8; weak scaling keeps 32/GPU at every N).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set up, warm up,
+time K steps, print the result line. --dump-outputs DIR additionally
+writes what the last timed step computed (see dump_outputs). --full is
+where any further measurement (baselines, other precisions, per-kernel
+figures) belongs; today the benchmark has none, so it changes nothing.
 
 For N>1 the driver launches this under torch.distributed.run (one rank per
 GPU over RCCL); standalone invocation with --gpus>1 re-execs itself the
@@ -30,7 +36,54 @@ def parse_args():
     p.add_argument("--bucket_mb", type=int, default=25)
     p.add_argument("--graph_capture", type=int, default=None)
     p.add_argument("--use_hip_ops", type=int, default=1)
+    p.add_argument("--dump-outputs", dest="dump_outputs", default=None,
+                   metavar="DIR",
+                   help="write the last timed step's results as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the extra measurements beyond the headline "
+                        "figure (none today)")
     return p.parse_args()
+
+
+# cap for each --dump-outputs array: 4M x fp32 = 16 MB
+DUMP_MAX_ELEMS = 4 * 1024 * 1024
+
+
+def dump_outputs(out_dir, engine, loss):
+    """Write what the last timed step left with its caller and that
+    repeats from run to run, as float32 .npy files:
+
+      loss.npy    the step's return value, shape (1,)
+      bn_var.npy  every BN's running_var in named_buffers() order, as the
+                  step's forward updated it: one value per channel of
+                  every conv+BN in the model
+
+    An array above DUMP_MAX_ELEMS elements is cut to that many by a fixed
+    seeded index sample. Nothing from backward or the update is written:
+    the gradients of the untrained network, their norms and the momentum
+    do not repeat between two runs of one build, and the parameters do not
+    move at the benchmark's warmup LR (docs/benchmarks.md, "Comparing two
+    builds", has the measurements)."""
+    import numpy as np
+    import torch
+
+    def flat(tensors):
+        out = torch.cat([t.detach().float().reshape(-1).cpu() for t in tensors])
+        if out.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(
+                out.numel(), size=DUMP_MAX_ELEMS, replace=False))
+            out = out[torch.from_numpy(idx)]
+        return out
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": flat([loss])}
+    bn_var = [b for name, b in engine.model.named_buffers()
+              if name.endswith("running_var")]
+    if bn_var:  # a model without BN has only its loss to show
+        arrays["bn_var"] = flat(bn_var)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.numpy().astype(np.float32, copy=False))
 
 
 def maybe_reexec(args):
@@ -92,9 +145,10 @@ def main():
     if use_cuda:
         torch.cuda.synchronize()
     t0 = time.monotonic()
+    loss = None
     for _ in range(args.steps):
         x, y = loader.next()
-        engine.replay_step(x, y)
+        loss = engine.replay_step(x, y)
     if use_cuda:
         torch.cuda.synchronize()
     edist.barrier(engine.device)
@@ -116,6 +170,8 @@ def main():
 
     peak_gb = (round(torch.cuda.max_memory_allocated() / 2**30, 2)
                if use_cuda else None)
+    if rank == 0 and args.dump_outputs and loss is not None:
+        dump_outputs(args.dump_outputs, engine, loss)
     if rank == 0:
         result = {
             "metric": "img/s",
