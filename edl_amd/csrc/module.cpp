@@ -19,6 +19,14 @@ extern "C" void launch_kd_ce_fwd_bf16(const void*, const void*, float*, int, int
                                       hipStream_t);
 extern "C" void launch_kd_ce_bwd_bf16(const void*, const void*, void*, float, int,
                                       int, hipStream_t);
+extern "C" void launch_softmax_ce_fwd(const void*, int, const long long*,
+                                      const long long*, const float*, float*,
+                                      float*, int*, float, int, int,
+                                      hipStream_t);
+extern "C" void launch_softmax_ce_bwd(const void*, int, const float*,
+                                      const long long*, const long long*,
+                                      const float*, const float*, void*, float,
+                                      float, int, int, hipStream_t);
 extern "C" int bn_stats_grid(long long, int);
 extern "C" int bn_bwd_grid(long long, int);
 extern "C" void launch_bn_stats(const void*, float*, int, long long, int,
@@ -155,6 +163,79 @@ torch::Tensor kd_ce_backward(torch::Tensor s, torch::Tensor t, double gout_over_
   } else {
     TORCH_CHECK(false, "kd_ce: fp32/bf16 only");
   }
+  return ds;
+}
+
+// shared argument checks of softmax_ce_forward/backward; returns the
+// (y_b, lam) device pointers, both null without mixup
+std::pair<const long long*, const float*> check_softmax_ce_inputs(
+    const torch::Tensor& s, const torch::Tensor& ya,
+    const c10::optional<torch::Tensor>& yb,
+    const c10::optional<torch::Tensor>& lam) {
+  TORCH_CHECK(s.is_cuda() && ya.device() == s.device(),
+              "softmax_ce: logits and labels on one GPU required");
+  TORCH_CHECK(s.dim() == 2 && s.size(0) >= 1 && s.size(1) >= 1,
+              "softmax_ce: [B,C] logits expected");
+  TORCH_CHECK(s.scalar_type() == torch::kFloat32 ||
+                  s.scalar_type() == torch::kBFloat16,
+              "softmax_ce: fp32/bf16 only");
+  TORCH_CHECK(s.is_contiguous(), "softmax_ce: contiguous logits required");
+  TORCH_CHECK(s.numel() < (1LL << 31), "softmax_ce: B*C < 2^31");
+  const int64_t B = s.size(0);
+  TORCH_CHECK(ya.scalar_type() == torch::kInt64 && ya.dim() == 1 &&
+                  ya.numel() == B && ya.is_contiguous(),
+              "softmax_ce: labels must be contiguous int64 [B]");
+  TORCH_CHECK(yb.has_value() == lam.has_value(),
+              "softmax_ce: labels_b and lam go together");
+  if (!yb.has_value()) return {nullptr, nullptr};
+  TORCH_CHECK(yb->is_cuda() && yb->scalar_type() == torch::kInt64 &&
+                  yb->dim() == 1 && yb->numel() == B && yb->is_contiguous(),
+              "softmax_ce: labels_b must be contiguous int64 [B] on the GPU");
+  TORCH_CHECK(lam->is_cuda() && lam->scalar_type() == torch::kFloat32 &&
+                  lam->dim() == 1 && lam->numel() == B && lam->is_contiguous(),
+              "softmax_ce: lam must be contiguous fp32 [B] on the GPU");
+  return {(const long long*)yb->data_ptr<int64_t>(), lam->data_ptr<float>()};
+}
+
+std::vector<torch::Tensor> softmax_ce_forward(torch::Tensor s, torch::Tensor ya,
+                                              c10::optional<torch::Tensor> yb,
+                                              c10::optional<torch::Tensor> lam,
+                                              double eps) {
+  // -> (loss_row f32 [B], lse f32 [B], rank i32 [B]); see softmax_ce.hip
+  auto mix = check_softmax_ce_inputs(s, ya, yb, lam);
+  const int B = (int)s.size(0), C = (int)s.size(1);
+  auto opts = s.options().dtype(torch::kFloat32);
+  auto loss_row = torch::empty({B}, opts);
+  auto lse = torch::empty({B}, opts);
+  auto rank = torch::empty({B}, s.options().dtype(torch::kInt32));
+  launch_softmax_ce_fwd(s.data_ptr(), s.scalar_type() == torch::kBFloat16,
+                        (const long long*)ya.data_ptr<int64_t>(), mix.first,
+                        mix.second, loss_row.data_ptr<float>(),
+                        lse.data_ptr<float>(), rank.data_ptr<int>(), (float)eps,
+                        B, C, cur_stream());
+  return {loss_row, lse, rank};
+}
+
+torch::Tensor softmax_ce_backward(torch::Tensor s, torch::Tensor lse,
+                                  torch::Tensor ya,
+                                  c10::optional<torch::Tensor> yb,
+                                  c10::optional<torch::Tensor> lam, double eps,
+                                  torch::Tensor gout, double inv_B) {
+  // gout: DEVICE fp32 scalar (no host read, so the call is graph-capturable)
+  auto mix = check_softmax_ce_inputs(s, ya, yb, lam);
+  const int B = (int)s.size(0), C = (int)s.size(1);
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat32 &&
+                  lse.numel() == B && lse.is_contiguous(),
+              "softmax_ce: lse must be contiguous fp32 [B] on the GPU");
+  TORCH_CHECK(gout.is_cuda() && gout.scalar_type() == torch::kFloat32 &&
+                  gout.numel() == 1,
+              "softmax_ce: gout must be a fp32 GPU scalar");
+  auto ds = torch::empty_like(s);
+  launch_softmax_ce_bwd(s.data_ptr(), s.scalar_type() == torch::kBFloat16,
+                        lse.data_ptr<float>(),
+                        (const long long*)ya.data_ptr<int64_t>(), mix.first,
+                        mix.second, gout.data_ptr<float>(), ds.data_ptr(),
+                        (float)eps, (float)inv_B, B, C, cur_stream());
   return ds;
 }
 
@@ -924,6 +1005,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lr_dev") = py::none());
   m.def("kd_ce_forward", &kd_ce_forward, "KD soft-label CE forward -> per-row loss");
   m.def("kd_ce_backward", &kd_ce_backward, "KD soft-label CE backward -> dlogits");
+  m.def("softmax_ce_forward", &softmax_ce_forward,
+        "hard-label CE (label smoothing, optional mixup) fwd -> "
+        "(loss_row, lse, rank)",
+        py::arg("s"), py::arg("labels"), py::arg("labels_b") = py::none(),
+        py::arg("lam") = py::none(), py::arg("eps") = 0.0);
+  m.def("softmax_ce_backward", &softmax_ce_backward,
+        "hard-label CE bwd -> dlogits (gout is a device scalar)",
+        py::arg("s"), py::arg("lse"), py::arg("labels"), py::arg("labels_b"),
+        py::arg("lam"), py::arg("eps"), py::arg("gout"), py::arg("inv_B"));
   m.def("bn_fwd_train", &bn_fwd_train,
         "fused NHWC bf16 BN(+add)+ReLU train fwd -> (y, mean, invstd, mask)",
         py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("rmean"),

@@ -144,6 +144,9 @@ class BNReLU2d(nn.Module):
             # Recomputing per forward cost ~4 tiny kernels x ~104 BN
             # layers per ResNeXt101 teacher fwd (~300 ms/s of pure launch
             # + elementwise overhead in the distill teacher trace r2c41).
+            # The version key does NOT see kernel writes (bn_fwd_train,
+            # fused_sgd, graph replay go through raw pointers):
+            # TrainerEngine.evaluate() invalidates _eval_ver explicitly.
             ver = (self.weight._version, self.bias._version,
                    self.running_mean._version, self.running_var._version)
             if getattr(self, "_eval_ver", None) != ver:

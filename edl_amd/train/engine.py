@@ -111,6 +111,8 @@ class TrainerEngine:
         dgc=False,
         dgc_ratio=0.01,
         dgc_rampup=0,
+        fused_ce=False,
+        track_accuracy=False,
     ):
         self.model_name = model
         self.per_device_batch = per_device_batch
@@ -134,6 +136,14 @@ class TrainerEngine:
         # dist_strategy.forward_recompute, train_with_fleet.py:322-325)
         self.dgc_cfg = (dgc, dgc_ratio, dgc_rampup)  # optional sparse allreduce
         self.dgc = None
+        # hard-label loss on the fused softmax-CE kernel (ops.functional.
+        # softmax_cross_entropy) instead of F.cross_entropy; mixup labels
+        # always take it (torch has no two-label loss)
+        self.fused_ce = fused_ce
+        # keep the true-class rank of the last train step as a DEVICE
+        # tensor (top-k correct is last_rank < k); no host sync
+        self.track_accuracy = track_accuracy
+        self.last_rank = None
 
         self.env = None
         self.device = None
@@ -342,7 +352,27 @@ class TrainerEngine:
         )
 
     # ---- the step ----
-    def _loss(self, logits, labels, teacher_logits=None):
+    def _hard_loss(self, logits, labels, labels_b=None, lam=None):
+        """The hard-label term. Default: F.cross_entropy on fp32 logits.
+        With fused_ce, mixup labels (torch has no two-label loss) or
+        track_accuracy (only the fused pass produces the rank) it runs on
+        the fused softmax-CE kernel, which takes the autocast logits as
+        they are (no .float() copy). The rank is that of `labels`, so it
+        is kept only for un-mixed batches."""
+        if not (self.fused_ce or self.track_accuracy or labels_b is not None):
+            return F.cross_entropy(logits.float(), labels,
+                                   label_smoothing=self.label_smoothing)
+        from ..ops.functional import softmax_cross_entropy
+
+        loss, rank = softmax_cross_entropy(
+            logits, labels, label_smoothing=self.label_smoothing,
+            labels_b=labels_b, lam=lam, return_rank=True)
+        if self.track_accuracy and labels_b is None:
+            self.last_rank = rank
+        return loss
+
+    def _loss(self, logits, labels, teacher_logits=None, labels_b=None,
+              lam=None):
         if teacher_logits is not None:
             # KD soft-label cross-entropy (reference
             # example/distill/resnet/train_with_fleet.py:254-259: student
@@ -352,20 +382,21 @@ class TrainerEngine:
             kd = kd_soft_cross_entropy(logits, teacher_logits)
             if self.kd_alpha >= 1.0:
                 return kd
-            ce = F.cross_entropy(logits.float(), labels,
-                                 label_smoothing=self.label_smoothing)
+            ce = self._hard_loss(logits, labels, labels_b, lam)
             return self.kd_alpha * kd + (1 - self.kd_alpha) * ce
-        return F.cross_entropy(logits.float(), labels,
-                               label_smoothing=self.label_smoothing)
+        return self._hard_loss(logits, labels, labels_b, lam)
 
-    def train_step(self, images, labels, teacher_logits=None):
+    def train_step(self, images, labels, teacher_logits=None, labels_b=None,
+                   lam=None):
+        """One step. labels_b/lam (given together): mixup labels and the
+        per-row weight of `labels`, see data/mixup.py."""
         self.reducer.zero_grad()
         self._prefill_derived_async()
         with _mark("edl.forward"):
             with torch.autocast(device_type=self.device.type, dtype=self.dtype,
                                 enabled=self.dtype != torch.float32):
                 logits = self.model(images)
-            loss = self._loss(logits, labels, teacher_logits)
+            loss = self._loss(logits, labels, teacher_logits, labels_b, lam)
         with _mark("edl.backward"):
             if self._prefill_stream is not None:
                 # dgrad kernels read the prefilled repacks (see
@@ -439,10 +470,12 @@ class TrainerEngine:
                 m.prefill_derived()
 
     # ---- hipGraph capture ----
-    def maybe_capture(self, images, labels):
+    def maybe_capture(self, images, labels, labels_b=None, lam=None):
         """Capture the full train step (fwd+bwd+allreduce+opt) as ONE hip
         graph. CNN steps at bs 32/GPU are launch-bound; replaying a single
         graph removes per-kernel launch gaps (guide §launches-baseline).
+        With labels_b/lam the captured step is the mixup step and
+        replay_step must be fed mixup batches too.
         Returns True if capture succeeded."""
         if self.device.type != "cuda" or self._graph is not None:
             return False
@@ -465,19 +498,27 @@ class TrainerEngine:
         try:
             self._static["x"] = images.clone()
             self._static["y"] = labels.clone()
+            mix = {}
+            if labels_b is not None:
+                self._static["y_b"] = labels_b.clone()
+                self._static["lam"] = lam.to(torch.float32).clone()
+                mix = {"labels_b": self._static["y_b"],
+                       "lam": self._static["lam"]}
             torch.cuda.synchronize()
             # warmup on a side stream (required before capture)
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 for _ in range(3):
-                    self.train_step(self._static["x"], self._static["y"])
+                    self.train_step(self._static["x"], self._static["y"],
+                                    **mix)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
             step_before = self.global_step
             with torch.cuda.graph(g):
-                self._static["loss"] = self.train_step(self._static["x"], self._static["y"])
+                self._static["loss"] = self.train_step(
+                    self._static["x"], self._static["y"], **mix)
             self.global_step = step_before  # capture itself is not a step
             self._graph = g
             log.info("captured train step as hipGraph")
@@ -488,15 +529,87 @@ class TrainerEngine:
             self._static = {}
             return False
 
-    def replay_step(self, images, labels):
+    def replay_step(self, images, labels, labels_b=None, lam=None):
         """Run one training step; uses the captured graph when available."""
         if self._graph is not None:
+            if (labels_b is not None) != ("y_b" in self._static):
+                raise ValueError(
+                    "replay_step: the captured step was %s mixup labels"
+                    % ("built with" if "y_b" in self._static else
+                       "built without"))
             self._static["x"].copy_(images, non_blocking=True)
             self._static["y"].copy_(labels, non_blocking=True)
+            if labels_b is not None:
+                self._static["y_b"].copy_(labels_b, non_blocking=True)
+                self._static["lam"].copy_(lam, non_blocking=True)
             self._graph.replay()
             self.global_step += 1
             return self._static["loss"]
-        return self.train_step(images, labels)
+        return self.train_step(images, labels, labels_b=labels_b, lam=lam)
+
+    # ---- evaluation ----
+    def evaluate(self, loader, steps):
+        """Validation pass (reference train_with_fleet.py test_prog: loss /
+        acc_top1 / acc_top5 per epoch) over `steps` batches of
+        loader.next() -> (x, y). Plain CE (no smoothing) and the rank of
+        the true class from ONE fused pass per batch; sums stay on the
+        device, one all_reduce over the world, one host sync at the end.
+        -> {"loss", "acc1", "acc5", "samples"} over all ranks."""
+        from ..ops.bnrelu import BNReLU2d
+        from ..ops.conv import bump_weight_epoch
+        from ..ops.functional import softmax_cross_entropy
+
+        # DO NOT remove as redundant: both eval-side caches are keyed on
+        # counters that the training step's writers never move.
+        # BNReLU2d caches the eval scale/shift on the _version of
+        # weight/bias/running stats, but bn_fwd_train, fused_sgd on the
+        # flat bucket and hipGraph replay write those tensors through raw
+        # pointers, which never bumps _version; Conv2dFast caches its
+        # repacked weights on the weight epoch, which only the host-side
+        # FusedSGD.step() bumps — not a graph replay. Without these two
+        # lines an eval after more training serves the first eval's values.
+        bump_weight_epoch()
+        for m in self.model.modules():
+            if isinstance(m, BNReLU2d):
+                m._eval_ver = None
+        # weights loaded outside an optimizer step (model.load_state_dict
+        # after setup) have not reached the bf16 compute mirrors yet
+        self._refresh_bf16_mirrors()
+
+        was_training = self.model.training
+        self.model.eval()
+        # [loss_sum, correct1, correct5, count]; the count is known on
+        # the host and joins the device sums once, after the loop
+        acc = torch.zeros(4, dtype=torch.float64, device=self.device)
+        seen = 0
+        try:
+            with torch.no_grad():
+                for _ in range(steps):
+                    x, y = loader.next()
+                    with torch.autocast(device_type=self.device.type,
+                                        dtype=self.dtype,
+                                        enabled=self.dtype != torch.float32):
+                        logits = self.model(x)
+                    loss, rank = softmax_cross_entropy(
+                        logits, y, label_smoothing=0.0, return_rank=True)
+                    n = y.shape[0]
+                    seen += n
+                    acc[:3] += torch.stack([
+                        loss.double() * n, (rank < 1).sum().double(),
+                        (rank < 5).sum().double()])
+        finally:
+            self.model.train(was_training)
+        acc[3] = seen
+        import torch.distributed as dist
+
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            if dist.get_backend() != "nccl":
+                acc = acc.cpu()
+            dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+        loss_sum, c1, c5, count = acc.tolist()  # the one host sync
+        div = max(count, 1.0)
+        return {"loss": loss_sum / div, "acc1": c1 / div, "acc5": c5 / div,
+                "samples": int(count)}
 
     # ---- epoch driver ----
     def train_epoch(self, epoch, loader, steps, log_every=50, on_step=None,
@@ -507,8 +620,8 @@ class TrainerEngine:
         loss = None
         for it in range(start_step, steps):
             self.set_lr(self.scaled_lr(epoch, it / max(1, steps)))
-            x, y = loader.next()
-            loss = self.replay_step(x, y)
+            # (x, y), or (x, y_a, y_b, lam) from a data.mixup.MixupLoader
+            loss = self.replay_step(*loader.next())
             imgs_done += self.global_batch
             if on_step:
                 on_step(epoch, it)

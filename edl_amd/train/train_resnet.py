@@ -18,6 +18,7 @@ import torch
 
 from ..cluster.status import TrainStatus, save_train_status
 from ..coord.client import CoordClient
+from ..data.mixup import MixupLoader
 from ..data.synthetic import SyntheticImageNet
 from ..utils.log import get_logger
 from . import dist as edist
@@ -50,6 +51,16 @@ def parse_args(argv=None):
     p.add_argument("--bucket_mb", type=int, default=25)
     p.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     p.add_argument("--profile", action="store_true")
+    # reference train_with_fleet.py: --use_label_smoothing /
+    # --label_smoothing_epsilon, --use_mixup / --mixup_alpha, and the
+    # per-epoch test_prog pass (loss / acc_top1 / acc_top5)
+    p.add_argument("--label_smoothing", type=float, default=0.1)
+    p.add_argument("--use_mixup", type=int, default=0)
+    p.add_argument("--mixup_alpha", type=float, default=0.2)
+    p.add_argument("--fused_ce", type=int, default=0,
+                   help="hard-label loss on the fused softmax-CE kernel")
+    p.add_argument("--eval_steps", type=int, default=0,
+                   help="validation batches after each epoch (0 = no eval)")
     return p.parse_args(argv)
 
 
@@ -70,6 +81,8 @@ def main(argv=None):
         checkpoint_dir=ckpt_dir,
         use_hip_ops=bool(args.use_hip_ops) and torch.cuda.is_available(),
         graph_capture=None if args.graph_capture is None else bool(args.graph_capture),
+        label_smoothing=args.label_smoothing,
+        fused_ce=bool(args.fused_ce),
     ).setup(tenv)
 
     # status reporting back to the control plane (reference TrainStatus flow,
@@ -97,6 +110,14 @@ def main(argv=None):
         loader = SyntheticImageNet(
             args.batch_size, engine.device, image_shape=shape,
             channels_last=cl, seed=1234 + engine.env.global_rank,
+        )
+
+    eval_loader = None
+    if args.eval_steps > 0:
+        # held-out synthetic batches: a seed of their own
+        eval_loader = SyntheticImageNet(
+            args.batch_size, engine.device, image_shape=shape,
+            channels_last=cl, seed=987654 + engine.env.global_rank,
         )
 
     def plane_epoch_loader():
@@ -138,12 +159,22 @@ def main(argv=None):
                 continue
         else:
             ep_loader, ep_steps = loader, args.steps_per_epoch
+        if args.use_mixup:
+            ep_loader = MixupLoader(
+                ep_loader, args.mixup_alpha,
+                seed=4321 + 1000 * epoch + engine.env.global_rank)
         stats = engine.train_epoch(
             epoch, ep_loader, ep_steps, on_step=on_step,
             start_step=engine.start_step if epoch == engine.start_epoch else 0)
         if engine.env.is_rank0:
             log.info("epoch %d done: %.1f img/s (world=%d, global_batch=%d)",
                      epoch, stats["img_per_s"], engine.world_size, engine.global_batch)
+        if args.eval_steps > 0:
+            ev = engine.evaluate(eval_loader, args.eval_steps)
+            if engine.env.is_rank0:
+                log.info("epoch %d eval: loss=%.4f acc1=%.4f acc5=%.4f "
+                         "(%d samples)", epoch, ev["loss"], ev["acc1"],
+                         ev["acc5"], ev["samples"])
         engine.save_checkpoint(epoch)
     if engine.ckpt is not None:
         engine.ckpt.wait()
