@@ -39,6 +39,24 @@ __device__ __forceinline__ F8 load8(const bf16* p) {
   return o;
 }
 
+// load8 whose 16-byte load stays ONE dwordx4: where the consumer masks
+// single elements (the ReLU select in the dx kernels) LLVM narrows the
+// vector load back into ushort/dwordx2/dword/ushort pieces despite the
+// alignment (seen in the .s of bn_bwd_dx_kernel<RELU>); the empty asm
+// makes the four dwords opaque so the load cannot be split.
+__device__ __forceinline__ F8 load8_whole(const bf16* p) {
+  uint4 raw = *reinterpret_cast<const uint4*>(__builtin_assume_aligned(p, 16));
+  asm volatile("" : "+v"(raw.x), "+v"(raw.y), "+v"(raw.z), "+v"(raw.w));
+  F8 o;
+  const unsigned w[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    o.v[2 * i] = __uint_as_float(w[i] << 16);
+    o.v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+  }
+  return o;
+}
+
 __device__ __forceinline__ void store8(bf16* p, const F8& x) {
   uint4 raw;
   ushort* u = reinterpret_cast<ushort*>(&raw);
@@ -277,6 +295,74 @@ __global__ void bn_apply_kernel(
   }
 }
 
+// Padded-layout addressing shared by the *_pad kernels below: flat octet
+// index j over [N, Hp, Wp, C/8] -> destination pixel `pix` and, for
+// interior pixels, the unpadded row. pix < 2^31 (host-checked), so the
+// Wp/Hp splits are 32-bit unsigned divides; the octet split keeps the
+// pow2 shift/mask form of bn_apply_kernel.
+struct PadIdx {
+  int oct;
+  unsigned pix;
+  long long row;  // unpadded NHWC row, or -1 on the halo
+};
+
+__device__ __forceinline__ PadIdx pad_index(const long long j, const int c8,
+                                            const bool p2, const int c8l,
+                                            const int H, const int W) {
+  PadIdx o;
+  o.oct = p2 ? (int)(j & (c8 - 1)) : (int)(j % c8);
+  o.pix = (unsigned)(p2 ? (j >> c8l) : (j / c8));
+  const unsigned Wp = (unsigned)W + 2u, Hp = (unsigned)H + 2u;
+  const unsigned t = o.pix / Wp;
+  const unsigned w = o.pix - t * Wp - 1u;  // wraps to huge on the halo
+  const unsigned n = t / Hp;
+  const unsigned h = t - n * Hp - 1u;
+  o.row = (h < (unsigned)H && w < (unsigned)W)
+              ? ((long long)n * H + h) * W + w
+              : -1;
+  return o;
+}
+
+// K3p: bn_apply (ReLU + mask, no residual) that writes y straight into the
+// zero-halo padded layout [N, H+2, W+2, C] the implicit-GEMM 3x3 kernels
+// read — the following conv skips its pad_nhwc pass. Iterates the PADDED
+// index space: interior octets get the normal value and mask byte (mask
+// stays indexed by the unpadded octet), halo octets get zeros. The halo is
+// rewritten on every launch, so uninitialised storage and hipGraph replay
+// are both safe.
+__global__ void bn_apply_pad_kernel(
+    const bf16* __restrict__ x, bf16* __restrict__ yp,
+    unsigned char* __restrict__ mask, const float* __restrict__ scale,
+    const float* __restrict__ shift, const int Nimg, const int H, const int W,
+    const int C) {
+  const int c8 = C >> 3;
+  const bool p2 = (c8 & (c8 - 1)) == 0;
+  const int c8l = 31 - __clz((unsigned)c8);
+  const long long total = (long long)Nimg * (H + 2) * (W + 2) * c8;
+  long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (; j < total; j += stride) {
+    const PadIdx p = pad_index(j, c8, p2, c8l, H, W);
+    const int c0 = p.oct * 8;
+    bf16* dst = yp + (long long)p.pix * C + c0;
+    if (p.row < 0) {
+      *reinterpret_cast<uint4*>(__builtin_assume_aligned(dst, 16)) =
+          uint4{0, 0, 0, 0};
+      continue;
+    }
+    F8 v = load8(x + p.row * C + c0);
+    unsigned char mb = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      v.v[k] = fmaf(v.v[k], scale[c0 + k], shift[c0 + k]);
+      if (v.v[k] > 0.0f) mb |= (1u << k);
+      v.v[k] = fmaxf(v.v[k], 0.0f);
+    }
+    mask[p.row * c8 + p.oct] = mb;
+    store8(dst, v);
+  }
+}
+
 // ---------------- backward ----------------
 
 // B1: per-channel reductions s1 = sum(dy_eff), s2 = sum(dy_eff * xhat),
@@ -483,6 +569,54 @@ __global__ void bn_bwd_dx_kernel(
       }
     }
     store8(dx + eoff, o);
+  }
+}
+
+// B3p: bn_bwd_dx (training, no residual) storing dx into the zero-halo
+// padded layout [N, H+2, W+2, C]: the producing conv's dgrad and wgrad
+// read it in place of a pad_nhwc copy. Same per-element math as
+// bn_bwd_dx_kernel; halo written on every launch (see bn_apply_pad_kernel).
+template <bool RELU>
+__global__ void bn_bwd_dx_pad_kernel(
+    const bf16* __restrict__ dy, const unsigned char* __restrict__ mask,
+    const bf16* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ gamma,
+    const float* __restrict__ sums, bf16* __restrict__ dxp, const int Nimg,
+    const int H, const int W, const int C) {
+  const int c8 = C >> 3;
+  const bool p2 = (c8 & (c8 - 1)) == 0;
+  const int c8l = 31 - __clz((unsigned)c8);
+  const long long total = (long long)Nimg * (H + 2) * (W + 2) * c8;
+  const float inv_m = 1.0f / (float)((long long)Nimg * H * W);
+  long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (; j < total; j += stride) {
+    const PadIdx p = pad_index(j, c8, p2, c8l, H, W);
+    const int c0 = p.oct * 8;
+    bf16* dst = dxp + (long long)p.pix * C + c0;
+    if (p.row < 0) {
+      *reinterpret_cast<uint4*>(__builtin_assume_aligned(dst, 16)) =
+          uint4{0, 0, 0, 0};
+      continue;
+    }
+    const long long eoff = p.row * C + c0;
+    F8 g = load8_whole(dy + eoff);
+    if (RELU) {
+      const unsigned mb = mask[p.row * c8 + p.oct];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) g.v[k] = (mb >> k) & 1 ? g.v[k] : 0.0f;
+    }
+    F8 xv = load8(x + eoff);
+    F8 o;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int c = c0 + k;
+      const float is = invstd[c];
+      const float xhat = (xv.v[k] - mean[c]) * is;
+      o.v[k] = gamma[c] * is *
+               (g.v[k] - sums[c] * inv_m - xhat * sums[C + c] * inv_m);
+    }
+    store8(dst, o);
   }
 }
 
@@ -840,6 +974,35 @@ extern "C" void launch_bn_bwd_dx(const void* dy, const unsigned char* mask,
     else CASE(false, false, false);
   }
 #undef CASE
+}
+
+extern "C" void launch_bn_apply_pad(const void* x, void* yp,
+                                    unsigned char* mask, const float* scale,
+                                    const float* shift, int Nimg, int H, int W,
+                                    int C, hipStream_t s) {
+  const long long total = (long long)Nimg * (H + 2) * (W + 2) * (C >> 3);
+  const int grid = elementwise_grid(total, 256);
+  hipLaunchKernelGGL(bn_apply_pad_kernel, dim3(grid), dim3(256), 0, s,
+                     (const bf16*)x, (bf16*)yp, mask, scale, shift, Nimg, H, W,
+                     C);
+}
+
+extern "C" void launch_bn_bwd_dx_pad(const void* dy, const unsigned char* mask,
+                                     const void* x, const float* mean,
+                                     const float* invstd, const float* gamma,
+                                     const float* sums, void* dxp, int Nimg,
+                                     int H, int W, int C, bool relu,
+                                     hipStream_t s) {
+  const long long total = (long long)Nimg * (H + 2) * (W + 2) * (C >> 3);
+  const int grid = elementwise_grid(total, 256);
+  if (relu)
+    hipLaunchKernelGGL((bn_bwd_dx_pad_kernel<true>), dim3(grid), dim3(256), 0,
+                       s, (const bf16*)dy, mask, (const bf16*)x, mean, invstd,
+                       gamma, sums, (bf16*)dxp, Nimg, H, W, C);
+  else
+    hipLaunchKernelGGL((bn_bwd_dx_pad_kernel<false>), dim3(grid), dim3(256), 0,
+                       s, (const bf16*)dy, nullptr, (const bf16*)x, mean,
+                       invstd, gamma, sums, (bf16*)dxp, Nimg, H, W, C);
 }
 
 extern "C" void launch_bn_bwd_fused(const void* dy, const unsigned char* mask,

@@ -78,7 +78,7 @@ __device__ __forceinline__ int tn_swz(int r) {
 // drains every glds per iteration — guide 'pipelining across barriers';
 // costs 96 KB LDS -> 1 block/CU).
 template <int BN1, int BN2, int KW, bool G3 = false, bool TR = false,
-          bool DEEP = false, bool G3S = false>
+          bool DEEP = false, bool G3S = false, bool APAD = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     float* __restrict__ C, const int N1, const int N2, const int K,
@@ -142,6 +142,19 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
                    Cin +
            g3_ci0;
   };
+  // APAD (G3): A = dY is itself stored in the zero-halo padded
+  // layout [N, Ho+2, Wo+2, N1] (written by the BN backward) — row m maps
+  // to the interior pixel (oy+1, ox+1), the A-side twin of b_row
+  static_assert(!APAD || (G3 && !G3S), "APAD is a G3 mode");
+  auto a_row = [&](long long k) -> const bf16* {
+    if constexpr (!APAD) return A + k * N1 + t1;
+    const int m = (int)k;
+    const int hw = Ho * Wo;
+    const int n = m / hw, rem = m % hw;
+    const int oy = rem / Wo, ox = rem % Wo;
+    return A + ((long long)(n * (Ho + 2) + oy + 1) * (Wo + 2) + ox + 1) * N1 +
+           t1;
+  };
   // G3S: full per-column source address (ncol = pre-swizzle col offset)
   auto b_src = [&](long long k, int ncol) -> const bf16* {
     const int m = (int)k;
@@ -186,11 +199,11 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
       if constexpr (TR) {
         int k, noff;
         tr_kn(ch, k, noff);
-        src = A + (k0 + k) * N1 + t1 + noff;
+        src = a_row(k0 + k) + noff;
       } else {
         const int r = ch * (64 / SLOTS_A) + lane / SLOTS_A;
         const int gslot = (lane % SLOTS_A) ^ tn_swz(r);
-        src = A + (k0 + r) * N1 + t1 + gslot * 8;
+        src = a_row(k0 + r) + gslot * 8;
       }
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)src,
@@ -233,7 +246,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
         noff = ((lane % SLOTS_A) ^ tn_swz(r)) * 8;
       }
       bf16x8 v = {};
-      if (k0 + r < K) v = *(const bf16x8*)(A + (k0 + r) * N1 + t1 + noff);
+      if (k0 + r < K) v = *(const bf16x8*)(a_row(k0 + r) + noff);
       *(__attribute__((address_space(3))) bf16x8*)(
           (__attribute__((address_space(3))) char*)(abase) + ch * 1024 +
           lane * 16) = v;
@@ -550,6 +563,49 @@ extern "C" void launch_gemm_tn3x3_splitk(const void* dy, const void* xpad,
                        dim3(256), lds, s, (const bf16*)dy, (const bf16*)xpad,
                        C, Cout, N2, M, Ho, Wo, Hp, Wp, Cin, stride, perm);
 #undef TN3_LAUNCH
+}
+
+template <int B1, int B2, int W, bool TR>
+static void tn3_apad_launch(dim3 grid, int lds, hipStream_t s, const void* dyp,
+                            const void* xpad, float* C, int Cout, int N2, int M,
+                            int Ho, int Wo, int Hp, int Wp, int Cin, int stride,
+                            int perm) {
+  hipLaunchKernelGGL(
+      (gemm_tn_kernel<B1, B2, W, true, TR, false, false, true>), grid,
+      dim3(256), lds, s, (const bf16*)dyp, (const bf16*)xpad, C, Cout, N2, M,
+      Ho, Wo, Hp, Wp, Cin, stride, perm);
+}
+
+extern "C" void launch_gemm_tn3x3_splitk_apad(const void* dyp,
+                                              const void* xpad, float* C,
+                                              int Cout, int Cin, int M, int Ho,
+                                              int Wo, int Hp, int Wp,
+                                              int stride, int splitk, int perm,
+                                              hipStream_t s) {
+  // launch_gemm_tn3x3_splitk with dY read from its own zero-halo padded
+  // layout [N, Ho+2, Wo+2, Cout] (APAD row map); same tile picks
+  const int N2 = 9 * Cin;
+  const bool b1 = Cout % 128 == 0, b2 = Cin % 128 == 0;
+  const int BN1 = b1 ? 128 : 64, BN2 = b2 ? 128 : 64;
+  const dim3 grid((Cout / BN1) * (N2 / BN2), splitk);
+  const int lds = (4 / ((BN1 / 64) * (BN2 / 64))) * 2 *
+                  (64 * BN1 * 2 + 64 * BN2 * 2);
+  const bool tr = tn_use_tr();
+#define APAD_ARGS \
+  grid, lds, s, dyp, xpad, C, Cout, N2, M, Ho, Wo, Hp, Wp, Cin, stride, perm
+  if (b1 && b2) {
+    if (tr) tn3_apad_launch<128, 128, 1, true>(APAD_ARGS);
+    else tn3_apad_launch<128, 128, 1, false>(APAD_ARGS);
+  } else if (b1) {
+    if (tr) tn3_apad_launch<128, 64, 2, true>(APAD_ARGS);
+    else tn3_apad_launch<128, 64, 2, false>(APAD_ARGS);
+  } else if (b2) {
+    if (tr) tn3_apad_launch<64, 128, 2, true>(APAD_ARGS);
+    else tn3_apad_launch<64, 128, 2, false>(APAD_ARGS);
+  } else {
+    tn3_apad_launch<64, 64, 4, false>(APAD_ARGS);
+  }
+#undef APAD_ARGS
 }
 
 extern "C" void launch_gemm_tn3x3_small(const void* dy, const void* xpad,

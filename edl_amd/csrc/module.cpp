@@ -100,6 +100,16 @@ extern "C" void launch_bn_bwd_dx(const void*, const unsigned char*, const void*,
                                  const float*, const float*, const float*,
                                  const float*, void*, void*, long long, int,
                                  bool, bool, bool, hipStream_t);
+extern "C" void launch_bn_apply_pad(const void*, void*, unsigned char*,
+                                    const float*, const float*, int, int, int,
+                                    int, hipStream_t);
+extern "C" void launch_bn_bwd_dx_pad(const void*, const unsigned char*,
+                                     const void*, const float*, const float*,
+                                     const float*, const float*, void*, int,
+                                     int, int, int, bool, hipStream_t);
+extern "C" void launch_gemm_tn3x3_splitk_apad(const void*, const void*, float*,
+                                              int, int, int, int, int, int,
+                                              int, int, int, int, hipStream_t);
 
 namespace {
 
@@ -284,13 +294,29 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
                                         double eps,
                                         c10::optional<torch::Tensor> res,
                                         bool relu,
-                                        c10::optional<torch::Tensor> pre_part) {
-  // x: [M, C] contiguous view of an NHWC tensor (Python side reshapes)
+                                        c10::optional<torch::Tensor> pre_part,
+                                        c10::optional<std::vector<int64_t>> pad_hw) {
+  // x: [M, C] contiguous view of an NHWC tensor (Python side reshapes).
+  // pad_hw = (H, W): y is returned as the zero-halo padded buffer
+  // [N, H+2, W+2, C] the 3x3 implicit-GEMM kernels read (relu, no res).
   const int64_t C = gamma.numel();
   TORCH_CHECK(x.dim() == 2 && x.size(1) == C && x.is_contiguous(),
               "bn: x must be a contiguous [M, C] view");
   check_bn_inputs(x, C);
   const long long M = x.numel() / C;
+  int64_t pad_n = 0, pad_h = 0, pad_w = 0;
+  if (pad_hw.has_value()) {
+    TORCH_CHECK(pad_hw->size() == 2, "bn: pad_hw = (H, W)");
+    pad_h = (*pad_hw)[0];
+    pad_w = (*pad_hw)[1];
+    TORCH_CHECK(relu && !res.has_value(),
+                "bn: pad_hw needs relu and no residual");
+    TORCH_CHECK(pad_h >= 1 && pad_w >= 1 && M >= 1 && M % (pad_h * pad_w) == 0,
+                "bn: pad_hw does not divide the rows of x");
+    pad_n = M / (pad_h * pad_w);
+    TORCH_CHECK(pad_n * (pad_h + 2) * (pad_w + 2) < (1LL << 31),
+                "bn: padded pixel count must stay below 2^31");
+  }
   auto opts = gamma.options().dtype(torch::kFloat32);
   const int grid = bn_stats_grid(M, (int)C);
   auto partial = torch::empty({grid, 2 * C}, opts);
@@ -298,7 +324,8 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
   auto invstd = torch::empty({C}, opts);
   auto scale = torch::empty({C}, opts);
   auto shift = torch::empty({C}, opts);
-  auto y = torch::empty_like(x);
+  auto y = pad_n ? torch::empty({pad_n, pad_h + 2, pad_w + 2, C}, x.options())
+                 : torch::empty_like(x);
   // 1-bit/channel ReLU mask for the backward (one byte per channel octet)
   auto msk = relu ? torch::empty({M, C / 8}, x.options().dtype(torch::kUInt8))
                   : torch::empty({0}, x.options().dtype(torch::kUInt8));
@@ -331,6 +358,13 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
                      rmean.defined() ? rmean.data_ptr<float>() : nullptr,
                      rvar.defined() ? rvar.data_ptr<float>() : nullptr,
                      (float)momentum, (float)eps, M, (int)C, s);
+  if (pad_n) {
+    launch_bn_apply_pad(x.data_ptr(), y.data_ptr(),
+                        (unsigned char*)msk.data_ptr(),
+                        scale.data_ptr<float>(), shift.data_ptr<float>(),
+                        (int)pad_n, (int)pad_h, (int)pad_w, (int)C, s);
+    return {y, mean, invstd, msk};
+  }
   launch_bn_apply(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr,
                   y.data_ptr(),
                   relu ? (unsigned char*)msk.data_ptr() : nullptr,
@@ -358,14 +392,35 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
                                   torch::Tensor gamma, bool relu, bool add,
                                   bool training,
                                   c10::optional<torch::Tensor> dgamma_acc,
-                                  c10::optional<torch::Tensor> dbeta_acc) {
+                                  c10::optional<torch::Tensor> dbeta_acc,
+                                  c10::optional<std::vector<int64_t>> pad_hw) {
+  // pad_hw = (H, W): dx comes back as the zero-halo padded buffer
+  // [N, H+2, W+2, C] (training, no residual, three-kernel route only; the
+  // single-launch EDL_BN_BWD_FUSED route returns the plain [M, C] dx and
+  // the caller tells the two apart by dx.dim()).
   const int64_t C = gamma.numel();
   check_bn_inputs(x, C);
   const long long M = x.numel() / C;
   auto opts = gamma.options().dtype(torch::kFloat32);
   const int grid = bn_bwd_grid(M, (int)C);
   auto sums = torch::empty({2, C}, opts);
-  auto dx = torch::empty_like(x);
+  // read per call (not static) so tests can A/B via os.environ
+  const char* fenv = getenv("EDL_BN_BWD_FUSED");
+  const bool fused_bwd = fenv ? atoi(fenv) != 0 : false;
+  int64_t pad_n = 0, pad_h = 0, pad_w = 0;
+  if (pad_hw.has_value() && !(fused_bwd && training)) {
+    TORCH_CHECK(pad_hw->size() == 2, "bn_bwd: pad_hw = (H, W)");
+    pad_h = (*pad_hw)[0];
+    pad_w = (*pad_hw)[1];
+    TORCH_CHECK(training && !add, "bn_bwd: pad_hw needs training, no residual");
+    TORCH_CHECK(pad_h >= 1 && pad_w >= 1 && M >= 1 && M % (pad_h * pad_w) == 0,
+                "bn_bwd: pad_hw does not divide the rows of x");
+    pad_n = M / (pad_h * pad_w);
+    TORCH_CHECK(pad_n * (pad_h + 2) * (pad_w + 2) < (1LL << 31),
+                "bn_bwd: padded pixel count must stay below 2^31");
+  }
+  auto dx = pad_n ? torch::empty({pad_n, pad_h + 2, pad_w + 2, C}, x.options())
+                  : torch::empty_like(x);
   auto dres = add ? torch::empty_like(x) : torch::Tensor();
   auto s = cur_stream();
   auto dyc = dy.is_contiguous() ? dy : dy.contiguous();
@@ -389,9 +444,6 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
                 "bn_bwd: dbeta_acc fp32 [C]");
     db_acc = dbeta_acc->data_ptr<float>();
   }
-  // read per call (not static) so tests can A/B via os.environ
-  const char* fenv = getenv("EDL_BN_BWD_FUSED");
-  const bool fused_bwd = fenv ? atoi(fenv) != 0 : false;
   if (fused_bwd && training) {
     // one launch: reduce + last-block finalize + dx (grid-wide flag sync);
     // ws = persistent per-device {arrive, flag, depart} ints, self-resetting
@@ -429,6 +481,14 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
                        partial.data_ptr<float>(), grid, M, (int)C, relu, s);
   launch_bn_bwd_finalize(partial.data_ptr<float>(), grid, sums.data_ptr<float>(),
                          (int)C, db_acc, dg_acc, s);
+  if (pad_n) {
+    launch_bn_bwd_dx_pad(dyc.data_ptr(), mp, x.data_ptr(),
+                         mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                         gamma.data_ptr<float>(), sums.data_ptr<float>(),
+                         dx.data_ptr(), (int)pad_n, (int)pad_h, (int)pad_w,
+                         (int)C, relu, s);
+    return {dx, sums[1], sums[0], dres};
+  }
   launch_bn_bwd_dx(dyc.data_ptr(), mp, x.data_ptr(),
                    mean.data_ptr<float>(), invstd.data_ptr<float>(),
                    gamma.data_ptr<float>(), sums.data_ptr<float>(), dx.data_ptr(),
@@ -599,31 +659,67 @@ std::vector<torch::Tensor> conv3x3_small_fwd_stats(torch::Tensor x,
   return {y, bpart};
 }
 
-torch::Tensor conv3x3s2_dgrad(torch::Tensor dy, torch::Tensor wcat,
-                              int64_t H, int64_t W) {
+// ---- zero-halo padded NHWC buffers -------------------------------------
+// The 3x3 implicit-GEMM kernels read xp [N, H+2, W+2, C] with a zero
+// halo. The *_padded entry points take such a buffer (from pad_nhwc below,
+// or written directly by bn_fwd_train / bn_bwd with pad_hw) so a tensor is
+// padded once per step instead of once per consumer; the unsuffixed entry
+// points pad and forward to them.
+
+// x: 4-D channels_last bf16 -> xp [N, H+2, W+2, C]
+torch::Tensor pad_nhwc(torch::Tensor x) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
+                  x.scalar_type() == torch::kBFloat16 &&
+                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
+              "pad_nhwc: 4-D channels_last bf16");
+  const int Nimg = (int)x.size(0), C = (int)x.size(1);
+  const int H = (int)x.size(2), W = (int)x.size(3);
+  TORCH_CHECK(C % 8 == 0, "pad_nhwc: C % 8");
+  auto xp = torch::empty({Nimg, H + 2, W + 2, C}, x.options());
+  launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, H + 2, W + 2, C,
+                  cur_stream());
+  return xp;
+}
+
+void check_padded(const torch::Tensor& xp, int64_t H, int64_t W,
+                  const char* who) {
+  TORCH_CHECK(xp.is_cuda() && xp.dim() == 4 &&
+                  xp.scalar_type() == torch::kBFloat16 && xp.is_contiguous(),
+              who, ": xp must be a contiguous [N, H+2, W+2, C] bf16 buffer");
+  TORCH_CHECK(H >= 1 && W >= 1 && xp.size(1) == H + 2 && xp.size(2) == W + 2,
+              who, ": xp is not the padded layout of an H x W image");
+}
+
+torch::Tensor conv3x3s2_dgrad_padded(torch::Tensor dyp, torch::Tensor wcat,
+                                     int64_t H, int64_t W) {
   // stride-2 3x3 same-pad dgrad (parity decomposition, conv3x3.hip).
-  // dy: [N, Cout, Ho, Wo] channels_last bf16; wcat: [Cin, 9*Cout]
+  // dyp: zero-halo padded dY [N, Ho+2, Wo+2, Cout]; wcat: [Cin, 9*Cout]
   // (conv.py _repack_w3_s2dgrad). Returns dx2d [N*H*W, Cin] bf16.
-  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
-                  dy.scalar_type() == torch::kBFloat16 &&
-                  dy.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "s2dgrad: 4-D channels_last bf16 dy");
-  const int Nimg = (int)dy.size(0), Cout = (int)dy.size(1);
-  const int Ho = (int)dy.size(2), Wo = (int)dy.size(3);
+  const int64_t Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  check_padded(dyp, Ho, Wo, "s2dgrad");
+  const int Nimg = (int)dyp.size(0), Cout = (int)dyp.size(3);
   const int Cin = (int)(wcat.size(0));
   TORCH_CHECK(wcat.is_contiguous() && wcat.size(1) == 9 * Cout,
               "s2dgrad: wcat [Cin, 9*Cout]");
   TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "s2dgrad: C % 64");
-  TORCH_CHECK((H + 1) / 2 == Ho && (W + 1) / 2 == Wo, "s2dgrad: shape");
-  const int Hop = Ho + 2, Wop = Wo + 2;
-  auto s = cur_stream();
-  auto dyp = torch::empty({(long long)Nimg * Hop * Wop * Cout}, dy.options());
-  launch_pad_nhwc(dy.data_ptr(), dyp.data_ptr(), Nimg, Ho, Wo, Hop, Wop, Cout,
-                  s);
-  auto dx = torch::empty({(long long)Nimg * H * W, Cin}, dy.options());
+  auto dx = torch::empty({(long long)Nimg * H * W, Cin}, dyp.options());
   launch_conv3x3s2_dgrad(dyp.data_ptr(), wcat.data_ptr(), dx.data_ptr(), Nimg,
-                         (int)H, (int)W, Cin, Cout, Hop, Wop, s);
+                         (int)H, (int)W, Cin, Cout, (int)Ho + 2, (int)Wo + 2,
+                         cur_stream());
   return dx;
+}
+
+torch::Tensor conv3x3s2_dgrad(torch::Tensor dy, torch::Tensor wcat,
+                              int64_t H, int64_t W) {
+  // dy: [N, Cout, Ho, Wo] channels_last bf16 (pads, then the call above)
+  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
+                  dy.scalar_type() == torch::kBFloat16 &&
+                  dy.is_contiguous(torch::MemoryFormat::ChannelsLast),
+              "s2dgrad: 4-D channels_last bf16 dy");
+  TORCH_CHECK((H + 1) / 2 == dy.size(2) && (W + 1) / 2 == dy.size(3),
+              "s2dgrad: shape");
+  TORCH_CHECK(dy.size(1) % 64 == 0, "s2dgrad: C % 64");
+  return conv3x3s2_dgrad_padded(pad_nhwc(dy), wcat, H, W);
 }
 
 torch::Tensor repack_dgrad_w3(torch::Tensor w_smaj, int64_t ci,
@@ -707,27 +803,29 @@ torch::Tensor avgpool2x2_bwd(torch::Tensor dy, int64_t H, int64_t W) {
   return dx;
 }
 
-torch::Tensor conv3x3_wgrad_operand(torch::Tensor x, int64_t stride) {
-  // x: 4-D channels_last bf16 input of the conv -> [9*Cin, Mp] shifted
-  // transpose (pads internally).
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "wgrad_operand: 4-D channels_last bf16");
-  const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
-  const int Hp = H + 2, Wp = W + 2;
-  const int Hout = (H - 1) / (int)stride + 1;
-  const int Wout = (W - 1) / (int)stride + 1;
+torch::Tensor conv3x3_wgrad_operand_padded(torch::Tensor xp, int64_t H,
+                                           int64_t W, int64_t stride) {
+  // xp: zero-halo padded conv input [N, H+2, W+2, Cin] -> [9*Cin, Mp]
+  // shifted transpose.
+  check_padded(xp, H, W, "wgrad_operand");
+  TORCH_CHECK(stride == 1 || stride == 2, "wgrad_operand: stride 1 or 2");
+  const int Nimg = (int)xp.size(0), Cin = (int)xp.size(3);
+  const int Hp = (int)H + 2, Wp = (int)W + 2;
+  const int Hout = ((int)H - 1) / (int)stride + 1;
+  const int Wout = ((int)W - 1) / (int)stride + 1;
   const int M = Nimg * Hout * Wout;
   const int Mp = (M + 63) / 64 * 64;
-  auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * Cin}, x.options());
-  launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
-  auto out = torch::empty({(long long)9 * Cin, Mp}, x.options());
+  auto out = torch::empty({(long long)9 * Cin, Mp}, xp.options());
   launch_shift9_transpose(xp.data_ptr(), out.data_ptr(), M, Cin, Mp,
-                          Hout * Wout, Wout, Hp, Wp, (int)stride, s);
+                          Hout * Wout, Wout, Hp, Wp, (int)stride,
+                          cur_stream());
   return out;
+}
+
+torch::Tensor conv3x3_wgrad_operand(torch::Tensor x, int64_t stride) {
+  // x: 4-D channels_last bf16 input of the conv (pads, then the call above)
+  auto xp = pad_nhwc(x);
+  return conv3x3_wgrad_operand_padded(xp, x.size(2), x.size(3), stride);
 }
 
 torch::Tensor gemm_bt_splitk(torch::Tensor a, torch::Tensor b, int64_t splitk) {
@@ -792,31 +890,37 @@ torch::Tensor gemm_tn_splitk(torch::Tensor a, torch::Tensor b, int64_t splitk,
   return c;
 }
 
-torch::Tensor gemm_tn3x3_splitk(torch::Tensor dy2d, torch::Tensor x,
-                                int64_t stride, int64_t splitk,
-                                c10::optional<torch::Tensor> out) {
+torch::Tensor gemm_tn3x3_splitk_padded(torch::Tensor dy, torch::Tensor xp,
+                                       int64_t H64, int64_t W64,
+                                       int64_t stride, int64_t splitk,
+                                       c10::optional<torch::Tensor> out) {
   // conv3x3 wgrad, fully direct: fp32 dW3[Cout, 9*Cin] = dY^T @
-  // gather3x3(pad(x)) — no transpose_pad / shift9 materializations.
-  // dy2d: [M, Cout] bf16 (NHWC-flattened dY); x: 4-D channels_last bf16.
-  TORCH_CHECK(dy2d.is_cuda() && dy2d.dim() == 2 &&
-                  dy2d.scalar_type() == torch::kBFloat16,
-              "gemm_tn3x3: dy2d [M,Cout] bf16");
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "gemm_tn3x3: x 4-D channels_last bf16");
-  const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
+  // gather3x3(xp) — no transpose_pad / shift9 materializations.
+  // xp: zero-halo padded conv input [N, H+2, W+2, Cin] bf16.
+  // dy: [M, Cout] bf16 (NHWC-flattened dY), or dY in its own zero-halo
+  // padded layout [N, Ho+2, Wo+2, Cout] (4-D, as the BN backward writes
+  // it), read through the kernel's A-operand row map.
+  check_padded(xp, H64, W64, "gemm_tn3x3");
+  TORCH_CHECK(stride == 1 || stride == 2, "gemm_tn3x3: stride 1 or 2");
+  const bool dy_padded = dy.dim() == 4;
+  TORCH_CHECK(dy.is_cuda() && (dy.dim() == 2 || dy_padded) &&
+                  dy.scalar_type() == torch::kBFloat16,
+              "gemm_tn3x3: dy [M,Cout] or padded [N,Ho+2,Wo+2,Cout] bf16");
+  const int Nimg = (int)xp.size(0), Cin = (int)xp.size(3);
+  const int H = (int)H64, W = (int)W64;
   const int Hp = H + 2, Wp = W + 2;
   const int Ho = (H - 1) / (int)stride + 1, Wo = (W - 1) / (int)stride + 1;
   const int M = Nimg * Ho * Wo;
-  const int Cout = (int)dy2d.size(1);
-  TORCH_CHECK((int)dy2d.size(0) == M, "gemm_tn3x3: dy2d rows != N*Ho*Wo");
+  const int Cout = (int)dy.size(dy_padded ? 3 : 1);
+  if (dy_padded) {
+    check_padded(dy, Ho, Wo, "gemm_tn3x3 dy");
+    TORCH_CHECK(dy.size(0) == Nimg, "gemm_tn3x3: dy batch != xp batch");
+  } else {
+    TORCH_CHECK((int)dy.size(0) == M, "gemm_tn3x3: dy2d rows != N*Ho*Wo");
+  }
   TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "gemm_tn3x3: C % 64");
-  auto dyc = dy2d.contiguous();
+  auto dyc = dy.contiguous();
   auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * Cin}, x.options());
-  launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
   const int nchunks = (M + 63) / 64;
   if (splitk <= 0) {
     const int tiles = (Cout / (Cout % 128 == 0 ? 128 : 64)) *
@@ -838,12 +942,28 @@ torch::Tensor gemm_tn3x3_splitk(torch::Tensor dy2d, torch::Tensor x,
                 "gemm_tn3x3_splitk: out fp32 contiguous");
     perm = (c.dim() == 2 && c.size(1) == 9 * Cin) ? 0 : Cin;
   } else {
-    c = torch::zeros({Cout, 9 * Cin}, x.options().dtype(torch::kFloat32));
+    c = torch::zeros({Cout, 9 * Cin}, xp.options().dtype(torch::kFloat32));
   }
-  launch_gemm_tn3x3_splitk(dyc.data_ptr(), xp.data_ptr(), c.data_ptr<float>(),
-                           Cout, Cin, M, Ho, Wo, Hp, Wp, (int)stride,
-                           (int)splitk, perm, s);
+  if (dy_padded)
+    launch_gemm_tn3x3_splitk_apad(dyc.data_ptr(), xp.data_ptr(),
+                                  c.data_ptr<float>(), Cout, Cin, M, Ho, Wo,
+                                  Hp, Wp, (int)stride, (int)splitk, perm, s);
+  else
+    launch_gemm_tn3x3_splitk(dyc.data_ptr(), xp.data_ptr(),
+                             c.data_ptr<float>(), Cout, Cin, M, Ho, Wo, Hp, Wp,
+                             (int)stride, (int)splitk, perm, s);
   return c;
+}
+
+torch::Tensor gemm_tn3x3_splitk(torch::Tensor dy2d, torch::Tensor x,
+                                int64_t stride, int64_t splitk,
+                                c10::optional<torch::Tensor> out) {
+  // dy2d: [M, Cout] bf16; x: 4-D channels_last bf16 (pads, then the call
+  // above)
+  TORCH_CHECK(dy2d.dim() == 2, "gemm_tn3x3: dy2d [M,Cout] bf16");
+  auto xp = pad_nhwc(x);
+  return gemm_tn3x3_splitk_padded(dy2d, xp, x.size(2), x.size(3), stride,
+                                  splitk, out);
 }
 
 torch::Tensor transpose_pad(torch::Tensor x) {
@@ -858,26 +978,48 @@ torch::Tensor transpose_pad(torch::Tensor x) {
   return y;
 }
 
-torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
-  // x: 4-D channels_last bf16 [N, C, H, W]; w3: [Cout, 9*Cin] bf16
+// geometry shared by the padded-input 3x3 forward entry points
+struct Conv3x3Geom {
+  int Cin, Cout, Hp, Wp, Hout, Wout;
+  long long M;
+};
+
+Conv3x3Geom conv3x3_geom(const torch::Tensor& xp, const torch::Tensor& w3,
+                         int64_t stride, int64_t H, int64_t W) {
+  check_padded(xp, H, W, "conv3x3");
+  TORCH_CHECK(stride == 1 || stride == 2, "conv3x3: stride 1 or 2");
+  Conv3x3Geom g;
+  g.Cin = (int)xp.size(3);
+  g.Cout = (int)w3.size(0);
+  TORCH_CHECK(w3.size(1) == 9 * g.Cin && w3.is_contiguous(),
+              "conv3x3: w3 shape");
+  TORCH_CHECK(g.Cin % 64 == 0 && g.Cout % 64 == 0, "conv3x3: C % 64");
+  g.Hp = (int)H + 2;
+  g.Wp = (int)W + 2;
+  g.Hout = ((int)H + 2 - 3) / (int)stride + 1;
+  g.Wout = ((int)W + 2 - 3) / (int)stride + 1;
+  g.M = (long long)xp.size(0) * g.Hout * g.Wout;
+  return g;
+}
+
+void check_conv3x3_x(const torch::Tensor& x) {
   TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
                   x.scalar_type() == torch::kBFloat16,
               "conv3x3: 4-D bf16 GPU tensor required");
   TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast),
               "conv3x3: channels_last required");
-  TORCH_CHECK(stride == 1 || stride == 2, "conv3x3: stride 1 or 2");
-  const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
-  const int Cout = (int)w3.size(0);
-  TORCH_CHECK(w3.size(1) == 9 * Cin && w3.is_contiguous(), "conv3x3: w3 shape");
-  TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "conv3x3: C % 64");
-  const int Hp = H + 2, Wp = W + 2;
-  const int Hout = (H + 2 - 3) / (int)stride + 1;
-  const int Wout = (W + 2 - 3) / (int)stride + 1;
-  const long long M = (long long)Nimg * Hout * Wout;
+  TORCH_CHECK(x.size(1) % 64 == 0, "conv3x3: C % 64");
+}
+
+torch::Tensor conv3x3_fwd_padded(torch::Tensor xp, torch::Tensor w3,
+                                 int64_t stride, int64_t H, int64_t W) {
+  // xp: zero-halo padded input [N, H+2, W+2, Cin] bf16; w3: [Cout, 9*Cin]
+  const Conv3x3Geom g = conv3x3_geom(xp, w3, stride, H, W);
+  const int Cin = g.Cin, Cout = g.Cout, Hp = g.Hp, Wp = g.Wp;
+  const int Hout = g.Hout, Wout = g.Wout;
+  const long long M = g.M;
+  const torch::Tensor& x = xp;  // options source
   auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * Cin}, x.options());
-  launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
   const int splitk = conv3x3_pick_splitk((int)M, Cout, Cin);
   if (splitk > 1) {
     // CU-starved deep-K shape: fp32 split-K partials + cast
@@ -898,29 +1040,26 @@ torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
   return y;
 }
 
-std::vector<torch::Tensor> conv3x3_fwd_stats(torch::Tensor x, torch::Tensor w3,
-                                             int64_t stride) {
-  // conv3x3_fwd + BN stats partials of the output ([tiles_m, 2*Cout]).
-  // Split-K shapes can't fold stats (sumsq is nonlinear over partial
-  // sums) — the second return is then an undefined tensor (Python None).
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16,
-              "conv3x3: 4-D bf16 GPU tensor required");
-  TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "conv3x3: channels_last required");
-  TORCH_CHECK(stride == 1 || stride == 2, "conv3x3: stride 1 or 2");
-  const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
-  const int Cout = (int)w3.size(0);
-  TORCH_CHECK(w3.size(1) == 9 * Cin && w3.is_contiguous(), "conv3x3: w3 shape");
-  TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0, "conv3x3: C % 64");
-  const int Hp = H + 2, Wp = W + 2;
-  const int Hout = (H + 2 - 3) / (int)stride + 1;
-  const int Wout = (W + 2 - 3) / (int)stride + 1;
-  const long long M = (long long)Nimg * Hout * Wout;
+torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
+  // x: 4-D channels_last bf16 [N, C, H, W] (pads, then the call above)
+  check_conv3x3_x(x);
+  return conv3x3_fwd_padded(pad_nhwc(x), w3, stride, x.size(2), x.size(3));
+}
+
+std::vector<torch::Tensor> conv3x3_fwd_stats_padded(torch::Tensor xp,
+                                                    torch::Tensor w3,
+                                                    int64_t stride, int64_t H,
+                                                    int64_t W) {
+  // conv3x3_fwd_padded + BN stats partials of the output ([tiles_m,
+  // 2*Cout]). Split-K shapes can't fold stats (sumsq is nonlinear over
+  // partial sums) — the second return is then an undefined tensor (Python
+  // None).
+  const Conv3x3Geom g = conv3x3_geom(xp, w3, stride, H, W);
+  const int Cin = g.Cin, Cout = g.Cout, Hp = g.Hp, Wp = g.Wp;
+  const int Hout = g.Hout, Wout = g.Wout;
+  const long long M = g.M;
+  const torch::Tensor& x = xp;  // options source
   auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * Cin}, x.options());
-  launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
   const int splitk = conv3x3_pick_splitk((int)M, Cout, Cin);
   if (splitk > 1) {
     auto part = part_pool_get((int)M, Cout, x.options().dtype(torch::kFloat32));
@@ -944,6 +1083,13 @@ std::vector<torch::Tensor> conv3x3_fwd_stats(torch::Tensor x, torch::Tensor w3,
                  Hout * Wout, Wout, Hp, Wp, (int)stride, nullptr, 1,
                  bpart.data_ptr<float>(), s);
   return {y, bpart};
+}
+
+std::vector<torch::Tensor> conv3x3_fwd_stats(torch::Tensor x, torch::Tensor w3,
+                                             int64_t stride) {
+  check_conv3x3_x(x);
+  return conv3x3_fwd_stats_padded(pad_nhwc(x), w3, stride, x.size(2),
+                                  x.size(3));
 }
 
 torch::Tensor gemm_tn3x3_small(torch::Tensor dy2d, torch::Tensor x,
@@ -1018,7 +1164,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused NHWC bf16 BN(+add)+ReLU train fwd -> (y, mean, invstd, mask)",
         py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("rmean"),
         py::arg("rvar"), py::arg("momentum"), py::arg("eps"), py::arg("res"),
-        py::arg("relu"), py::arg("pre_part") = py::none());
+        py::arg("relu"), py::arg("pre_part") = py::none(),
+        py::arg("pad_hw") = py::none());
   m.def("bn_fwd_eval", &bn_fwd_eval, "fused NHWC bf16 BN(+add)+ReLU eval fwd");
   m.def("bn_bwd", &bn_bwd,
         "fused BN(+add)+ReLU bwd -> (dx, dgamma, dbeta, dres?)",
@@ -1026,7 +1173,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("mean"), pybind11::arg("invstd"), pybind11::arg("gamma"),
         pybind11::arg("relu"), pybind11::arg("add"), pybind11::arg("training"),
         pybind11::arg("dgamma_acc") = pybind11::none(),
-        pybind11::arg("dbeta_acc") = pybind11::none());
+        pybind11::arg("dbeta_acc") = pybind11::none(),
+        pybind11::arg("pad_hw") = pybind11::none());
+  m.def("pad_nhwc", &pad_nhwc,
+        "channels_last bf16 [N,C,H,W] -> zero-halo padded [N,H+2,W+2,C]");
+  m.def("conv3x3_fwd_padded", &conv3x3_fwd_padded,
+        "conv3x3_fwd on an already padded xp [N,H+2,W+2,Cin]", py::arg("xp"),
+        py::arg("w3"), py::arg("stride"), py::arg("H"), py::arg("W"));
+  m.def("conv3x3_fwd_stats_padded", &conv3x3_fwd_stats_padded,
+        "conv3x3_fwd_stats on an already padded xp", py::arg("xp"),
+        py::arg("w3"), py::arg("stride"), py::arg("H"), py::arg("W"));
+  m.def("conv3x3s2_dgrad_padded", &conv3x3s2_dgrad_padded,
+        "conv3x3s2_dgrad on an already padded dy [N,Ho+2,Wo+2,Cout]",
+        py::arg("dyp"), py::arg("wcat"), py::arg("H"), py::arg("W"));
+  m.def("gemm_tn3x3_splitk_padded", &gemm_tn3x3_splitk_padded,
+        "gemm_tn3x3_splitk on padded xp; dy [M,Cout] or padded 4-D",
+        py::arg("dy"), py::arg("xp"), py::arg("H"), py::arg("W"),
+        py::arg("stride"), py::arg("splitk") = 0, py::arg("out") = py::none());
+  m.def("conv3x3_wgrad_operand_padded", &conv3x3_wgrad_operand_padded,
+        "conv3x3_wgrad_operand on an already padded xp", py::arg("xp"),
+        py::arg("H"), py::arg("W"), py::arg("stride"));
   m.def("gemm_bt", &gemm_bt, "bf16 MFMA GEMM: C[M,N] = A[M,K] @ B[N,K]^T");
   m.def("conv3x3_fwd", &conv3x3_fwd,
         "implicit-GEMM 3x3 same-pad conv (stride 1/2) -> y2d [M, Cout]");

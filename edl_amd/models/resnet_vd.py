@@ -25,10 +25,15 @@ class ConvBN(nn.Module):
                               bias=False)
         self.bn = BNReLU2d(cout, act=act)
 
-    def forward(self, x):
-        # conv folds BN stats partials into its epilogue when training
-        y = self.conv(x, bn_stats=self.bn.training)
-        return self.bn(y, partials=self.conv.pop_bn_part())
+    def forward(self, x, pad_out=False):
+        # conv folds BN stats partials into its epilogue when training.
+        # The conv output feeds only this BN, so a 3x3 conv may take its
+        # dy from the BN backward in the padded layout (dx_pad).
+        # pad_out: the caller feeds the result to exactly one 3x3
+        # Conv2dFast — the BN writes that conv's padded input layout.
+        y = self.conv(x, bn_stats=self.bn.training, dx_pad=True)
+        return self.bn(y, partials=self.conv.pop_bn_part(), pad_out=pad_out,
+                       dx_pad=self.conv.pop_dy_pad())
 
 
 class VdShortcut(nn.Module):
@@ -69,8 +74,9 @@ class BottleneckVd(nn.Module):
 
     def forward(self, x):
         s = self.shortcut(x)
-        y = self.conv2(self.conv1(self.conv0(x)),
-                       bn_stats=self.bn_add.training)
+        # conv0's output has one consumer, conv1's 3x3
+        y0 = self.conv0(x, pad_out=self.conv1.conv.takes_padded())
+        y = self.conv2(self.conv1(y0), bn_stats=self.bn_add.training)
         return self.bn_add(y, s, partials=self.conv2.pop_bn_part())
 
 

@@ -13,6 +13,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import available, ext
+from . import conv as _conv
+from .conv import padded_interior
 
 
 def _direct_grad(p):
@@ -26,11 +28,24 @@ def _direct_grad(p):
 
 class _FusedBN(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x2d, gamma, beta, rmean, rvar, momentum, eps, res2d, relu,
-                pre_part=None):
+    def forward(ctx, x, gamma, beta, rmean, rvar, momentum, eps, res2d, relu,
+                pre_part=None, pad_out=None, dx_pad=None):
+        # x: the [M, C] view, or the 4-D channels_last tensor itself (then
+        # y comes back 4-D too). The two padded-layout hand-offs to a 3x3
+        # conv (conv.py) need the 4-D form on their side, because the
+        # interior of a padded buffer is no [M, C] view:
+        #  pad_out (list): y is written into the zero-halo padded buffer,
+        #    which is appended to the list; the [N, C, H, W] interior view
+        #    is returned. Needs relu, no residual.
+        #  dx_pad (list, 4-D x only): backward writes dx padded, leaves
+        #    the buffer in the list (the producing conv's backward pops
+        #    it) and returns the interior view as the gradient.
+        ctx.shape4 = tuple(x.shape) if x.dim() == 4 else None
+        x2d = _to_2d(x) if x.dim() == 4 else x
+        assert ctx.shape4 is not None or (pad_out is None and dx_pad is None)
         y, mean, invstd, mask = ext().bn_fwd_train(
             x2d, gamma, beta, rmean, rvar, momentum, eps, res2d, relu,
-            pre_part
+            pre_part, ctx.shape4[2:] if pad_out is not None else None
         )
         # backward reads the 1-bit ReLU mask instead of y (16x fewer bytes)
         ctx.save_for_backward(x2d, mask, mean, invstd, gamma)
@@ -38,20 +53,32 @@ class _FusedBN(torch.autograd.Function):
         ctx.has_res = res2d is not None
         ctx.dg_t = _direct_grad(gamma)
         ctx.db_t = _direct_grad(beta)
-        return y
+        ctx.dx_pad = dx_pad
+        if pad_out is not None:
+            pad_out.append(y)
+            return padded_interior(y)
+        return _from_2d(y, ctx.shape4) if ctx.shape4 is not None else y
 
     @staticmethod
     def backward(ctx, dy):
         x2d, mask, mean, invstd, gamma = ctx.saved_tensors
+        if dy.dim() == 4:
+            dy = _to_2d(dy)
         dx, dgamma, dbeta, dres = ext().bn_bwd(
             dy, mask, x2d, mean, invstd, gamma, ctx.relu, ctx.has_res, True,
-            ctx.dg_t, ctx.db_t
+            ctx.dg_t, ctx.db_t,
+            ctx.shape4[2:] if ctx.dx_pad is not None else None
         )
+        if dx.dim() == 4:  # padded [N, H+2, W+2, C]
+            ctx.dx_pad[:] = [dx]
+            dx = padded_interior(dx)
+        elif ctx.shape4 is not None:
+            dx = _from_2d(dx, ctx.shape4)
         return (dx,
                 None if ctx.dg_t is not None else dgamma,
                 None if ctx.db_t is not None else dbeta,
                 None, None, None, None,
-                dres if ctx.has_res else None, None, None)
+                dres if ctx.has_res else None, None, None, None, None)
 
 
 def _to_2d(t):
@@ -130,10 +157,27 @@ class BNReLU2d(nn.Module):
             y = F.relu(y)
         return y.to(x.dtype)
 
-    def _fused(self, x, res=None, partials=None):
+    def _fused(self, x, res=None, partials=None, pad_out=False, dx_pad=None):
         x2d = _to_2d(x)
         res2d = _to_2d(res) if res is not None else None
         if self.training:
+            # padded-layout hand-offs to a neighbouring 3x3 conv (see
+            # _FusedBN.forward); both are plain-BN(+ReLU) only
+            pad_out = (pad_out and self.act and res is None
+                       and _conv._PAD_ONCE and _conv._BN_PAD_OUT)
+            if res is not None or not (_conv._PAD_ONCE and _conv._BN_PAD_DX):
+                dx_pad = None
+            if pad_out or dx_pad is not None:
+                holder = [] if pad_out else None
+                y = _FusedBN.apply(
+                    x, self.weight, self.bias, self.running_mean,
+                    self.running_var, self.momentum, self.eps, None, self.act,
+                    partials, holder, dx_pad,
+                )
+                if pad_out:
+                    # the consumer (Conv2dFast) finds the padded buffer here
+                    y._edl_xp = holder[0]
+                return y
             y2d = _FusedBN.apply(
                 x2d, self.weight, self.bias, self.running_mean, self.running_var,
                 self.momentum, self.eps, res2d, self.act, partials,
@@ -159,15 +203,21 @@ class BNReLU2d(nn.Module):
                                     self._eval_shift, res2d, self.act)
         return _from_2d(y2d, x.shape)
 
-    def forward(self, x, res=None, partials=None):
+    def forward(self, x, res=None, partials=None, pad_out=False, dx_pad=None):
         # partials: BN stats pre-folded into the producing conv's
-        # epilogue ([tiles, 2C] fp32) — skips the stats kernel
+        # epilogue ([tiles, 2C] fp32) — skips the stats kernel.
+        # pad_out: the output feeds exactly one padded-input 3x3 conv —
+        # write it in the padded layout (returned tensor carries _edl_xp).
+        # dx_pad: the producing conv's pop_dy_pad() holder.
+        # Both are honoured on the fused training path only; everywhere
+        # else the conv pads for itself.
         if self.training:
             self._batches_seen += 1
         if self._use_fused(x, res):
             if self.training or not torch.is_grad_enabled():
                 return self._fused(x, res,
-                                   partials if self.training else None)
+                                   partials if self.training else None,
+                                   pad_out, dx_pad)
         if partials is not None:
             # capped partials come from a pooled buffer that the finalize
             # kernel normally returns clean; if we're not consuming them,

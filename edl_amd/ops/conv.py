@@ -101,6 +101,44 @@ _GROUPED_MINC = int(os.environ.get("EDL_CONV3X3_GROUPED_MINC", "16"))
 # skips its stats kernel — a full activation re-read, ~0.53 ms/step).
 _BN_STATS_FUSED = os.environ.get("EDL_BN_STATS_FUSED", "1") == "1"
 
+# Zero-halo padded buffers [N, H+2, W+2, C] of the 3x3 implicit-GEMM path.
+# Each stage keeps its own opt-out (0 = the previous behaviour):
+#  EDL_PAD_ONCE   the conv pads its input ONCE in forward and saves the
+#                 padded buffer; both wgrad routes read it (was: padded
+#                 again inside the wgrad binding).
+#  EDL_BN_PAD_OUT the preceding BN+ReLU writes its output straight into
+#                 the padded layout (bn_apply_pad_kernel); the conv's
+#                 forward pad disappears. Needs EDL_PAD_ONCE.
+#  EDL_BN_PAD_DX  the following BN's backward writes dx into the padded
+#                 layout (bn_bwd_dx_pad_kernel); dgrad and the gather
+#                 wgrad read it in place of the dy pad. Needs EDL_PAD_ONCE.
+#                 OPT-IN (default 0): measured -0.2% on top of the other
+#                 two (docs/kernels.md, NOTES_ROUND2.md negatives).
+_PAD_ONCE = os.environ.get("EDL_PAD_ONCE", "1") == "1"
+_BN_PAD_OUT = os.environ.get("EDL_BN_PAD_OUT", "1") == "1"
+_BN_PAD_DX = os.environ.get("EDL_BN_PAD_DX", "0") == "1"
+
+
+def padded_interior(xp):
+    """[N, C, H, W] view of the interior of a padded [N, H+2, W+2, C]."""
+    return xp[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2)
+
+
+def is_interior_of(t, xp):
+    """True iff t IS padded_interior(xp): same memory, shape and strides.
+    Anything else (a copy, a sum autograd made, a tensor from elsewhere)
+    is not, and its consumer pads it the ordinary way."""
+    if xp is None or xp.dim() != 4 or t.dim() != 4:
+        return False
+    n, hp, wp, c = xp.shape
+    return (t.dtype == xp.dtype and t.device == xp.device
+            and xp.is_contiguous()
+            and tuple(t.shape) == (n, c, hp - 2, wp - 2)
+            and tuple(t.stride()) == (hp * wp * c, 1, wp * c, c)
+            and t.data_ptr() == xp.data_ptr()
+            + (wp + 1) * c * xp.element_size())
+
+
 # Weight-derived tensors (bf16 casts, transposed/repacked layouts) are
 # immutable within one optimizer step; FusedSGD.step() bumps this epoch and
 # Conv2dFast caches per-epoch, removing ~100 small cast/copy kernels per
@@ -130,19 +168,39 @@ class _Conv3x3Hip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w_param, w_bf16, w3_cached, w3rot_cached, stride,
-                grad_tgt, part_out=None):
-        ctx.save_for_backward(x, w_bf16)
+                grad_tgt, part_out=None, xp=None, dyp_holder=None):
+        # xp: x already in the zero-halo padded layout (x is its interior
+        # view; written by the preceding BN) — else padded here, ONCE: the
+        # padded buffer is what backward's wgrad reads, so it is saved in
+        # place of x. dyp_holder: a list shared with the FOLLOWING BN,
+        # whose backward leaves its padded dx there (see backward).
+        e = ext()
+        n, ci, h, w = x.shape
+        ctx.padded = xp is not None or _PAD_ONCE
+        if ctx.padded:
+            if xp is None:
+                xp = e.pad_nhwc(x)
+            ctx.save_for_backward(xp, w_bf16)
+        else:
+            ctx.save_for_backward(x, w_bf16)
+        ctx.x_shape = (n, ci, h, w)
+        ctx.dyp_holder = dyp_holder
         ctx.stride = stride
         ctx.w3rot = w3rot_cached  # s1: rotated fwd repack; s2: s2dgrad wcat
         ctx.w_dtype = w_param.dtype
         ctx.grad_tgt = grad_tgt
         if part_out is not None:
-            y2d, part = ext().conv3x3_fwd_stats(x, w3_cached, stride)
+            if ctx.padded:
+                y2d, part = e.conv3x3_fwd_stats_padded(xp, w3_cached, stride,
+                                                       h, w)
+            else:
+                y2d, part = e.conv3x3_fwd_stats(x, w3_cached, stride)
             if part is not None:  # split-K shapes return None
                 part_out.append(part)
+        elif ctx.padded:
+            y2d = e.conv3x3_fwd_padded(xp, w3_cached, stride, h, w)
         else:
-            y2d = ext().conv3x3_fwd(x, w3_cached, stride)
-        n, _, h, w = x.shape
+            y2d = e.conv3x3_fwd(x, w3_cached, stride)
         ho = (h - 1) // stride + 1
         wo = (w - 1) // stride + 1
         co = w_param.shape[0]
@@ -150,21 +208,38 @@ class _Conv3x3Hip(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
+        x, weight = ctx.saved_tensors  # x: padded buffer when ctx.padded
         stride = ctx.stride
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        n, _, h, w = x.shape
-        if stride == 1:
+        n, cin, h, w = ctx.x_shape
+        ho = (h - 1) // stride + 1
+        wo = (w - 1) // stride + 1
+        # dy straight from the following BN's backward, already in the
+        # padded layout? Only if the gradient we were handed IS that
+        # buffer's interior — autograd may have summed or copied it.
+        dyp = None
+        if ctx.dyp_holder:
+            cand = ctx.dyp_holder.pop()
+            if is_interior_of(dy, cand):
+                dyp = cand
+        if dyp is None:
+            dy = dy.contiguous(memory_format=torch.channels_last)
+        if dyp is not None and stride == 1:
+            dx2d = ext().conv3x3_fwd_padded(dyp, ctx.w3rot, 1, ho, wo)
+            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
+        elif dyp is not None:
+            dx2d = ext().conv3x3s2_dgrad_padded(dyp, ctx.w3rot, h, w)
+            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
+        elif stride == 1:
             dx2d = ext().conv3x3_fwd(dy.to(torch.bfloat16), ctx.w3rot, 1)
-            dx = dx2d.view(n, h, w, x.shape[1]).permute(0, 3, 1, 2)
+            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
         elif ctx.w3rot is not None:
             # stride 2: parity-decomposed implicit-GEMM dgrad (4 class
             # launches, exact work) — replaces MIOpen's igemm_bwd
             dx2d = ext().conv3x3s2_dgrad(dy.to(torch.bfloat16), ctx.w3rot, h, w)
-            dx = dx2d.view(n, h, w, x.shape[1]).permute(0, 3, 1, 2)
+            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
         else:
             dx = torch.nn.grad.conv2d_input(
-                list(x.shape), weight, dy, stride=(stride, stride),
+                [n, cin, h, w], weight, dy, stride=(stride, stride),
                 padding=(1, 1))
         # wgrad: dW3[Cout, 9Cin] = dY^T @ shift9(x). Default: the direct
         # TN gather kernel reading dY and pad(x) in native NHWC layout
@@ -172,26 +247,38 @@ class _Conv3x3Hip(torch.autograd.Function):
         # transpose_pad(dy) [Cout, Mp] + shift9_transpose(x) [9Cin, Mp]
         # and run the split-K bt kernel.
         e = ext()
-        n = dy.shape[0]
         co = weight.shape[0]
         ci = weight.shape[1]
-        dy2d = dy.permute(0, 2, 3, 1).reshape(-1, co)
-        if _WGRAD == "tn" and ci <= _WGRAD3_MAXC:
+        none9 = (None,) * 9
+        if dyp is not None:
+            # only requested on the gather route (Conv2dFast.forward): the
+            # kernel reads dY through its A-operand row map
+            dya = dyp
+        else:
+            dya = dy.permute(0, 2, 3, 1).reshape(-1, co).to(torch.bfloat16)
+        if dyp is not None or (_WGRAD == "tn" and ci <= _WGRAD3_MAXC):
+            if ctx.padded:
+                def tn3(*out):
+                    return e.gemm_tn3x3_splitk_padded(dya, x, h, w, stride, 0,
+                                                      *out)
+            else:
+                def tn3(*out):
+                    return e.gemm_tn3x3_splitk(dya, x, stride, 0, *out)
             if ctx.grad_tgt is not None:
                 # accumulate straight into the bucket-view grad, laid out
                 # [Cout, Cin, 3, 3] (kernel epilogue remaps)
-                e.gemm_tn3x3_splitk(dy2d.to(torch.bfloat16), x, stride, 0,
-                                    ctx.grad_tgt)
-                return dx, None, None, None, None, None, None, None
-            dw3 = e.gemm_tn3x3_splitk(dy2d.to(torch.bfloat16), x, stride, 0)
+                tn3(ctx.grad_tgt)
+                return (dx,) + none9
+            dw3 = tn3()
         else:
             dw3 = e.gemm_bt_splitk(
-                e.transpose_pad(dy2d.to(torch.bfloat16)),
-                e.conv3x3_wgrad_operand(x, stride), 0)
+                e.transpose_pad(dya),
+                e.conv3x3_wgrad_operand_padded(x, h, w, stride) if ctx.padded
+                else e.conv3x3_wgrad_operand(x, stride), 0)
         dw = dw3.view(co, 3, 3, ci).permute(0, 3, 1, 2)  # fp32
         if dw.dtype != ctx.w_dtype:
             dw = dw.to(ctx.w_dtype)
-        return dx, dw, None, None, None, None, None, None
+        return (dx, dw) + none9[1:]
 
 
 def _small_cpt(cin):
@@ -409,25 +496,51 @@ class Conv2dFast(nn.Conv2d):
         self._bn_part = None
         return p
 
-    def forward(self, x, bn_stats=False):
+    def pop_dy_pad(self):
+        """The holder the LAST forward shares with the following BN (or
+        None): that BN's backward leaves its dx there in the padded layout
+        and this conv's backward reads it in place of padding dy."""
+        p = getattr(self, "_dy_pad", None)
+        self._dy_pad = None
+        return p
+
+    def _is_dense3x3(self):
+        return (self.kernel_size == (3, 3)
+                and self.groups == 1
+                and self.padding == (1, 1)
+                and self.stride[0] == self.stride[1]
+                and self.stride[0] in (1, 2)
+                and self.bias is None
+                and self.in_channels % 64 == 0
+                and self.out_channels % 64 == 0)
+
+    def takes_padded(self):
+        """True if this conv runs the padded-input 3x3 kernels and wants
+        the producing BN to write the padded layout (x._edl_xp)."""
+        return (_PAD_ONCE and _BN_PAD_OUT and _CONV3X3 == "hip"
+                and available() and self._is_dense3x3())
+
+    def forward(self, x, bn_stats=False, dx_pad=False):
+        # dx_pad: the caller feeds the output to exactly one BN and will
+        # hand it pop_dy_pad()
         self._bn_part = None
+        self._dy_pad = None
         bn_stats = bn_stats and _BN_STATS_FUSED
         if (
             _CONV3X3 == "hip"
             and x.is_cuda
             and available()
             and x.dtype == torch.bfloat16
-            and self.kernel_size == (3, 3)
-            and self.groups == 1
-            and self.padding == (1, 1)
-            and self.stride[0] == self.stride[1]
-            and self.stride[0] in (1, 2)
-            and self.bias is None
-            and self.in_channels % 64 == 0
-            and self.out_channels % 64 == 0
+            and self._is_dense3x3()
         ):
-            if not x.is_contiguous(memory_format=torch.channels_last):
-                x = x.contiguous(memory_format=torch.channels_last)
+            # x written by the preceding BN straight into the padded
+            # layout: the buffer rides on the tensor, and is used only if
+            # x still IS its interior view
+            xp = getattr(x, "_edl_xp", None) if _PAD_ONCE else None
+            if not is_interior_of(x, xp):
+                xp = None
+                if not x.is_contiguous(memory_format=torch.channels_last):
+                    x = x.contiguous(memory_format=torch.channels_last)
             co, ci = self.out_channels, self.in_channels
             cl = getattr(self.weight, "_edl_phys_shape", None) is not None
             mb = getattr(self.weight, "_edl_bf16", None)
@@ -468,10 +581,19 @@ class Conv2dFast(nn.Conv2d):
                     and torch.is_grad_enabled() and self.training):
                 grad_tgt = w.grad.permute(0, 2, 3, 1).reshape(co, 9 * ci)
             holder = [] if bn_stats else None
+            # padded dy from the following BN: gather-wgrad layers only
+            # (the deep route's transpose_pad needs a contiguous dy)
+            dyp_holder = None
+            if (dx_pad and _PAD_ONCE and _BN_PAD_DX and _WGRAD == "tn"
+                    and ci <= _WGRAD3_MAXC and w3rot is not None
+                    and torch.is_grad_enabled()):
+                dyp_holder = []
             y = _Conv3x3Hip.apply(x, self.weight, w_bf16, w3, w3rot,
-                                  self.stride[0], grad_tgt, holder)
+                                  self.stride[0], grad_tgt, holder, xp,
+                                  dyp_holder)
             if holder:
                 self._bn_part = holder[0]
+            self._dy_pad = dyp_holder
             return y
         if (
             # deep-stem 3x3s (3->32->32->64): small-channel kernel
