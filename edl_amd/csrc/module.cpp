@@ -110,11 +110,127 @@ extern "C" void launch_bn_bwd_dx_pad(const void*, const unsigned char*,
 extern "C" void launch_gemm_tn3x3_splitk_apad(const void*, const void*, float*,
                                               int, int, int, int, int, int,
                                               int, int, int, int, hipStream_t);
+extern "C" int dgc_workspace_words();
+extern "C" void launch_dgc_accumulate(const float*, float*, float*,
+                                      const float*, float, float, long long,
+                                      unsigned*, int, hipStream_t);
+extern "C" void launch_dgc_hist(const float*, long long, unsigned*, int,
+                                hipStream_t);
+extern "C" void launch_dgc_pick(unsigned*, int, unsigned, hipStream_t);
+extern "C" void launch_dgc_compact(float*, float*, long long, int*, unsigned,
+                                   unsigned*, hipStream_t);
+extern "C" void launch_dgc_scatter_add(float*, long long, const int*,
+                                       long long, hipStream_t);
 
 namespace {
 
 hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
+}
+
+// ---- DGC top-k compress / decode (dgc.hip) -------------------------------
+void dgc_check_flat(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+                  t.dim() == 1 && t.is_contiguous(),
+              "dgc: ", name, " must be a flat contiguous fp32 GPU tensor");
+  TORCH_CHECK(t.numel() >= 1 && t.numel() < (1LL << 31),
+              "dgc: 1 <= n < 2^31 required for ", name);
+}
+
+unsigned* dgc_ws_ptr(const torch::Tensor& ws, const torch::Tensor& like) {
+  TORCH_CHECK(ws.is_cuda() && ws.device() == like.device() &&
+                  ws.scalar_type() == torch::kInt32 && ws.is_contiguous() &&
+                  ws.numel() == dgc_workspace_words(),
+              "dgc: workspace must be the int32 GPU tensor of "
+              "dgc_workspace_words() zeros");
+  return reinterpret_cast<unsigned*>(ws.data_ptr<int>());
+}
+
+void dgc_check_k(int64_t k, const torch::Tensor& v) {
+  TORCH_CHECK(k >= 1 && k <= v.numel(), "dgc: 1 <= k <= n required");
+}
+
+int* dgc_payload_ptr(const torch::Tensor& payload, int64_t k,
+                     const torch::Tensor& like) {
+  TORCH_CHECK(payload.is_cuda() && payload.device() == like.device() &&
+                  payload.scalar_type() == torch::kInt32 &&
+                  payload.is_contiguous() && payload.dim() == 2 &&
+                  payload.size(0) == 2 && payload.size(1) == k,
+              "dgc: payload must be a contiguous int32 [2, k] GPU tensor");
+  return payload.data_ptr<int>();
+}
+
+void dgc_accumulate(torch::Tensor g, torch::Tensor u, torch::Tensor v,
+                    c10::optional<torch::Tensor> p, double mu, double wd,
+                    torch::Tensor ws, int64_t hist_copies) {
+  // u = mu*u + (g + wd*p); v += u; histogram of the top 11 bits of |v|
+  dgc_check_flat(g, "g");
+  dgc_check_flat(u, "u");
+  dgc_check_flat(v, "v");
+  TORCH_CHECK(g.numel() == u.numel() && g.numel() == v.numel() &&
+                  g.device() == u.device() && g.device() == v.device(),
+              "dgc: g, u, v must match in size and device");
+  const float* pp = nullptr;
+  if (p.has_value()) {
+    dgc_check_flat(*p, "p");
+    TORCH_CHECK(p->numel() == g.numel() && p->device() == g.device(),
+                "dgc: p must match g");
+    pp = p->data_ptr<float>();
+  }
+  TORCH_CHECK(hist_copies == 1 || hist_copies == 4, "dgc: hist_copies 1 or 4");
+  launch_dgc_accumulate(g.data_ptr<float>(), u.data_ptr<float>(),
+                        v.data_ptr<float>(), pp, (float)mu, (float)wd,
+                        (long long)g.numel(), dgc_ws_ptr(ws, g),
+                        (int)hist_copies, cur_stream());
+}
+
+void dgc_hist(torch::Tensor v, torch::Tensor ws, int64_t pass) {
+  dgc_check_flat(v, "v");
+  TORCH_CHECK(pass == 1 || pass == 2, "dgc_hist: pass 1 or 2");
+  launch_dgc_hist(v.data_ptr<float>(), (long long)v.numel(),
+                  dgc_ws_ptr(ws, v), (int)pass, cur_stream());
+}
+
+void dgc_pick(torch::Tensor v, torch::Tensor ws, int64_t pass, int64_t k) {
+  dgc_check_flat(v, "v");
+  dgc_check_k(k, v);
+  TORCH_CHECK(pass >= 0 && pass <= 2, "dgc_pick: pass 0..2");
+  launch_dgc_pick(dgc_ws_ptr(ws, v), (int)pass, (unsigned)k, cur_stream());
+}
+
+void dgc_compact(torch::Tensor v, torch::Tensor u, torch::Tensor payload,
+                 torch::Tensor ws) {
+  dgc_check_flat(v, "v");
+  dgc_check_flat(u, "u");
+  TORCH_CHECK(u.numel() == v.numel() && u.device() == v.device(),
+              "dgc: u must match v");
+  const int64_t k = payload.dim() == 2 ? payload.size(1) : -1;
+  dgc_check_k(k, v);
+  launch_dgc_compact(v.data_ptr<float>(), u.data_ptr<float>(),
+                     (long long)v.numel(), dgc_payload_ptr(payload, k, v),
+                     (unsigned)k, dgc_ws_ptr(ws, v), cur_stream());
+}
+
+void dgc_select(torch::Tensor v, torch::Tensor u, torch::Tensor payload,
+                torch::Tensor ws) {
+  // everything after dgc_accumulate: pick 0, (hist, pick) x 2, compact
+  const int64_t k = payload.dim() == 2 ? payload.size(1) : -1;
+  dgc_pick(v, ws, 0, k);
+  dgc_hist(v, ws, 1);
+  dgc_pick(v, ws, 1, k);
+  dgc_hist(v, ws, 2);
+  dgc_pick(v, ws, 2, k);
+  dgc_compact(v, u, payload, ws);
+}
+
+void dgc_scatter_add(torch::Tensor out, torch::Tensor payload) {
+  // out[idx] += val for one rank's payload; idx < 0 (empty slot) is skipped
+  dgc_check_flat(out, "out");
+  const int64_t k = payload.dim() == 2 ? payload.size(1) : -1;
+  TORCH_CHECK(k >= 1, "dgc: payload must be int32 [2, k]");
+  launch_dgc_scatter_add(out.data_ptr<float>(), (long long)out.numel(),
+                         dgc_payload_ptr(payload, k, out), (long long)k,
+                         cur_stream());
 }
 
 void fused_sgd(torch::Tensor p, torch::Tensor g, torch::Tensor m, double lr,
@@ -1149,6 +1265,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p"), py::arg("g"), py::arg("m"), py::arg("lr"),
         py::arg("momentum"), py::arg("weight_decay"), py::arg("grad_scale"),
         py::arg("lr_dev") = py::none());
+  m.def("dgc_workspace_words", &dgc_workspace_words,
+        "int32 words of the (zero-initialised) DGC select workspace");
+  m.def("dgc_accumulate", &dgc_accumulate,
+        "DGC: u = mu*u + (g + wd*p); v += u; radix-select pass 0 histogram",
+        py::arg("g"), py::arg("u"), py::arg("v"), py::arg("p"), py::arg("mu"),
+        py::arg("wd"), py::arg("ws"), py::arg("hist_copies") = 4);
+  m.def("dgc_hist", &dgc_hist, "DGC radix-select histogram pass 1 or 2",
+        py::arg("v"), py::arg("ws"), py::arg("pass_"));
+  m.def("dgc_pick", &dgc_pick, "DGC radix-select: fix one digit (pass 0..2)",
+        py::arg("v"), py::arg("ws"), py::arg("pass_"), py::arg("k"));
+  m.def("dgc_compact", &dgc_compact,
+        "DGC: write the selected (idx, bits) into payload [2,k]; zero v, u",
+        py::arg("v"), py::arg("u"), py::arg("payload"), py::arg("ws"));
+  m.def("dgc_select", &dgc_select,
+        "DGC: pick 0, (hist, pick) x 2 and compact, after dgc_accumulate",
+        py::arg("v"), py::arg("u"), py::arg("payload"), py::arg("ws"));
+  m.def("dgc_scatter_add", &dgc_scatter_add,
+        "DGC decode: out[idx] += val for one rank's payload",
+        py::arg("out"), py::arg("payload"));
   m.def("kd_ce_forward", &kd_ce_forward, "KD soft-label CE forward -> per-row loss");
   m.def("kd_ce_backward", &kd_ce_backward, "KD soft-label CE backward -> dlogits");
   m.def("softmax_ce_forward", &softmax_ce_forward,

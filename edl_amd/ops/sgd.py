@@ -76,14 +76,22 @@ class FusedSGD:
         return out
 
     @torch.no_grad()
-    def step(self):
+    def step(self, momentum=None, weight_decay=None):
+        """momentum / weight_decay override the group's values for this
+        step only (None = the group's). DGC momentum correction steps
+        with 0.0, 0.0: both already live in its accumulators, and with
+        momentum 0 the momentum buffer just mirrors the update."""
         from .conv import bump_weight_epoch
 
         bump_weight_epoch()  # invalidate per-step weight-derived caches
         g0 = self.param_groups[0]
         lr, mu, wd = g0["lr"], g0["momentum"], g0["weight_decay"]
+        if momentum is not None:
+            mu = float(momentum)
+        if weight_decay is not None:
+            wd = float(weight_decay)
         for bk in self._materialize():
-            if self._use_ext:
+            if self._use_ext and bk["p"].is_cuda:
                 ext().fused_sgd(bk["p"], bk["g"], bk["m"], lr, mu, wd,
                                 self.grad_scale, self._lr_dev)
             else:

@@ -111,6 +111,9 @@ class TrainerEngine:
         dgc=False,
         dgc_ratio=0.01,
         dgc_rampup=0,
+        dgc_momentum_correction=False,
+        dgc_sparsity=None,
+        dgc_rampup_step=1,
         fused_ce=False,
         track_accuracy=False,
     ):
@@ -136,6 +139,19 @@ class TrainerEngine:
         # dist_strategy.forward_recompute, train_with_fleet.py:322-325)
         self.dgc_cfg = (dgc, dgc_ratio, dgc_rampup)  # optional sparse allreduce
         self.dgc = None
+        # dgc + dgc_momentum_correction: train/dgc.py DGCMomentum (local
+        # momentum, masking, sparsity ramp dgc_sparsity over
+        # dgc_rampup_step steps after dgc_rampup) instead of DGCCompressor;
+        # dgc_sparsity=None keeps the dgc_ratio knob: (1 - dgc_ratio,)
+        self.dgc_momentum_correction = bool(dgc_momentum_correction)
+        self.dgc_sparsity = (tuple(dgc_sparsity) if dgc_sparsity
+                             else (1.0 - dgc_ratio,))
+        self.dgc_rampup_step = dgc_rampup_step
+        if dgc and self.dgc_momentum_correction and self.scaler is not None:
+            raise ValueError(
+                "DGC momentum correction cannot run under the fp16 loss "
+                "scaler: a changing loss scale corrupts the accumulated "
+                "gradients (use bf16 or fp32)")
         # hard-label loss on the fused softmax-CE kernel (ops.functional.
         # softmax_cross_entropy) instead of F.cross_entropy; mixup labels
         # always take it (torch has no two-label loss)
@@ -199,12 +215,19 @@ class TrainerEngine:
         self.reducer = BucketedAllReducer(
             self.model.parameters(), bucket_cap_mb=self.bucket_mb
         )
-        if self.dgc_cfg[0]:
+        if self.dgc_cfg[0] and not self.dgc_momentum_correction:
             from .dgc import DGCCompressor
 
             self.dgc = DGCCompressor(self.reducer, self.dgc_cfg[1],
                                      self.dgc_cfg[2])
         self.opt = self._build_optimizer()
+        if self.dgc_cfg[0] and self.dgc_momentum_correction:
+            from .dgc import DGCMomentum
+
+            self.dgc = DGCMomentum(
+                self.reducer, self.opt, self.momentum, self.weight_decay,
+                rampup_begin_step=self.dgc_cfg[2],
+                rampup_step=self.dgc_rampup_step, sparsity=self.dgc_sparsity)
         if self.checkpoint_dir:
             self.ckpt = CheckpointManager(self.checkpoint_dir)
             self._resume()
@@ -408,7 +431,12 @@ class TrainerEngine:
             else:
                 loss.backward()
         with _mark("edl.allreduce_finalize"):
-            if self.dgc is not None:
+            opt_kw = {}
+            if self.dgc_momentum_correction and self.dgc is not None:
+                self.dgc.step(global_step=self.global_step + 1)
+                # DGC phase: momentum and weight decay already live in u
+                opt_kw = self.dgc.opt_overrides()
+            elif self.dgc is not None:
                 self.dgc.step()
             else:
                 self.reducer.finalize()
@@ -433,11 +461,11 @@ class TrainerEngine:
                     base = self.opt.grad_scale
                     self.opt.grad_scale = base * inv_scale
                     try:
-                        self.opt.step()
+                        self.opt.step(**opt_kw)
                     finally:
                         self.opt.grad_scale = base
                 else:
-                    self.opt.step()
+                    self.opt.step(**opt_kw)
             else:
                 scale = self.reducer.grad_scale * inv_scale
                 if scale != 1.0:
@@ -482,6 +510,9 @@ class TrainerEngine:
         if self.scaler is not None:
             # fp16 loss scaling is data-dependent control flow (inf check,
             # step skip) — not capturable as one static graph
+            return False
+        if self.dgc_momentum_correction and self.dgc is not None:
+            # k and the dense/DGC phase are host-side schedule state
             return False
         want = self.graph_capture
         if want is None:

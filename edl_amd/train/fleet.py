@@ -33,6 +33,9 @@ class DistributedStrategy:
     fuse_all_reduce_ops_mb: int = 25          # bucket size
     use_amp: bool = True                      # bf16 autocast
     use_dgc: bool = False                     # optional sparse allreduce
+    # Paddle's keys: rampup_begin_step, rampup_step, sparsity (a list).
+    # Non-empty (with use_dgc) = DGC with momentum correction.
+    dgc_configs: dict = field(default_factory=dict)
     use_recompute: bool = False
     extra: dict = field(default_factory=dict)
 
@@ -81,6 +84,15 @@ def distributed_engine(model_name="resnet50_vd", strategy=None, **kwargs):
     kwargs.setdefault("dtype", "bf16" if strategy.use_amp and
                       torch.cuda.is_available() else "fp32")
     kwargs.setdefault("dgc", strategy.use_dgc)
+    if strategy.use_dgc and strategy.dgc_configs:
+        cfg = dict(strategy.dgc_configs)
+        unknown = set(cfg) - {"rampup_begin_step", "rampup_step", "sparsity"}
+        if unknown:
+            raise ValueError("dgc_configs: unknown keys %s" % sorted(unknown))
+        kwargs.setdefault("dgc_momentum_correction", True)
+        kwargs.setdefault("dgc_rampup", cfg.get("rampup_begin_step", 0))
+        kwargs.setdefault("dgc_rampup_step", cfg.get("rampup_step", 1))
+        kwargs.setdefault("dgc_sparsity", cfg.get("sparsity", [0.999]))
     kwargs.setdefault("recompute", strategy.use_recompute)
     eng = TrainerEngine(model=model_name, **kwargs)
     eng.setup(_state["env"])

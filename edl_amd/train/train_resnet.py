@@ -61,6 +61,15 @@ def parse_args(argv=None):
                    help="hard-label loss on the fused softmax-CE kernel")
     p.add_argument("--eval_steps", type=int, default=0,
                    help="validation batches after each epoch (0 = no eval)")
+    # reference train_with_fleet.py --use_dgc / --rampup_begin_step
+    # (DGCMomentumOptimizer): DGC with momentum correction
+    p.add_argument("--use_dgc", type=int, default=0)
+    p.add_argument("--rampup_begin_step", type=int, default=0,
+                   help="dense all-reduce up to and including this step")
+    p.add_argument("--rampup_step", type=int, default=1,
+                   help="steps over which --dgc_sparsity is walked")
+    p.add_argument("--dgc_sparsity", default="0.999",
+                   help="comma list, e.g. 0.75,0.9375,0.984375,0.996,0.999")
     return p.parse_args(argv)
 
 
@@ -83,6 +92,11 @@ def main(argv=None):
         graph_capture=None if args.graph_capture is None else bool(args.graph_capture),
         label_smoothing=args.label_smoothing,
         fused_ce=bool(args.fused_ce),
+        dgc=bool(args.use_dgc),
+        dgc_momentum_correction=bool(args.use_dgc),
+        dgc_rampup=args.rampup_begin_step,
+        dgc_rampup_step=args.rampup_step,
+        dgc_sparsity=[float(x) for x in args.dgc_sparsity.split(",") if x],
     ).setup(tenv)
 
     # status reporting back to the control plane (reference TrainStatus flow,
