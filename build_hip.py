@@ -55,7 +55,11 @@ def build(verbose=True):
     ] + ["-I" + i for i in tp["includes"]] + ["-I" + CSRC]
 
     objs = []
-    hdr = [os.path.join(CSRC, "common.h")]
+    # every source includes launchers.h (the checked ABI), the kernels
+    # common.h too: any header change rebuilds every object
+    hdr = sorted(
+        os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")
+    )
     sources = sorted(
         f for f in os.listdir(CSRC) if f.endswith(".hip") or f.endswith(".cpp")
     )

@@ -5,6 +5,7 @@
 // Divisor = number of VALID elements in the (clamped) window — torch
 // semantics for unpadded ceil_mode pooling.
 #include "common.h"
+#include "launchers.h"
 
 using bf16 = __hip_bfloat16;
 

@@ -14,6 +14,7 @@
 // row-group; blocks grid-stride over rows and atomically fold per-channel
 // fp32 partials (distinct addresses — L2-rate, not contended).
 #include "common.h"
+#include "launchers.h"
 
 using bf16 = __hip_bfloat16;
 

@@ -4,16 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
-#define EDL_HIP_CHECK(expr)                                                   \
-  do {                                                                        \
-    hipError_t _e = (expr);                                                   \
-    if (_e != hipSuccess) {                                                   \
-      throw std::runtime_error(std::string("HIP error: ") +                   \
-                               hipGetErrorString(_e) + " at " __FILE__ ":" +  \
-                               std::to_string(__LINE__));                     \
-    }                                                                         \
-  } while (0)
-
 constexpr int kWave = 64;  // CDNA wavefront
 
 // Grid sizing for memory-bound elementwise kernels (guide G11): cap blocks,

@@ -15,6 +15,7 @@
 // the padded-row byte address for the A rows it stages (fixed across the
 // K loop); the k-tile adds shift_off[s] + 128*cb.
 #include "common.h"
+#include "launchers.h"
 
 using bf16 = __hip_bfloat16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -254,11 +255,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(
       }
     }
     __syncthreads();
-    // fold into <=192 partial rows (finalize latency/traffic cap): rows
-    // beyond the cap atomically add into row mtile %% cap (buffer
-    // pre-zeroed by the caller in that case)
+    // fold into <= kStatsPartRowCap partial rows (finalize latency/traffic
+    // cap): rows beyond the cap atomically add into row mtile %% cap
+    // (buffer pre-zeroed by the caller in that case)
     const int tiles_m = gridDim.x / (N / BN);
-    const int cap = tiles_m < 192 ? tiles_m : 192;
+    const int cap = tiles_m < kStatsPartRowCap ? tiles_m : kStatsPartRowCap;
     const int mtile = (bid / (N / BN)) % cap;
     float* dst = bn_part + (long long)mtile * 2 * N + n0;
     if (tiles_m > cap) {
@@ -445,7 +446,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_small_kernel(
         }
     }
     __syncthreads();
-    const int cap = (int)gridDim.x < 192 ? (int)gridDim.x : 192;
+    const int cap = (int)gridDim.x < kStatsPartRowCap ? (int)gridDim.x
+                                                      : kStatsPartRowCap;
     float* dst = bn_part + (long long)(bid % cap) * 2 * Cout_real;
     if ((int)gridDim.x > cap) {
       for (int i = threadIdx.x; i < Cout_real; i += blockDim.x) {
@@ -506,12 +508,20 @@ extern "C" void launch_pad_nhwc_cpad(const void* x, void* xp, int Nimg, int H,
                      (const bf16*)x, (bf16*)xp, H, W, Hp, Wp, Creal, Cpad);
 }
 
+// rows per block of conv3x3_small_kernel (its BM); the grid is one block
+// per m-tile, which is also the stats-partial row count before the cap
+constexpr int kSmallBM = 256;
+
+extern "C" int conv3x3_small_tiles_m(int M) {
+  return (M + kSmallBM - 1) / kSmallBM;
+}
+
 extern "C" void launch_conv3x3_small(const void* xp, const void* w3s, void* y,
                                      int M, int Cout_real, int cpt, int HW_out,
                                      int W_out, int Hp, int Wp, int stride,
                                      float* bn_part, hipStream_t s) {
-  constexpr int BM = 256;
-  const int grid = (M + BM - 1) / BM;
+  constexpr int BM = kSmallBM;
+  const int grid = conv3x3_small_tiles_m(M);
   const int lds_bytes = 2 * (BM * 64 * 2 + 64 * 64 * 2);
 #define SCASE(CPT)                                                          \
   hipLaunchKernelGGL((conv3x3_small_kernel<CPT>), dim3(grid), dim3(256),    \

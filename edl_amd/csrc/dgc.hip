@@ -20,6 +20,7 @@
 // it and its last pass resets the cursor, so a step needs no fill launch.
 // One workspace serves one stream at a time.
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

@@ -9,6 +9,7 @@
 // Memory-bound: 3 reads + 2 writes of 4 B per element; float4-vectorized
 // (16 B/lane, guide Guideline 13), grid-stride.
 #include "common.h"
+#include "launchers.h"
 
 extern "C" __global__ void fused_sgd_f32(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

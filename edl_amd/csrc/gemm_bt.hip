@@ -20,6 +20,7 @@
 //   * row-clamped A loads for the M tail (C-write is row-guarded)
 //   * two tile shapes: 128x128 (N % 128 == 0) and 256x64
 #include "common.h"
+#include "launchers.h"
 
 using bf16 = __hip_bfloat16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -302,7 +303,8 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     }
     __syncthreads();
     const int tiles_m_g = gridDim.x / tiles_n;
-    const int cap = tiles_m_g < 192 ? tiles_m_g : 192;
+    const int cap =
+        tiles_m_g < kStatsPartRowCap ? tiles_m_g : kStatsPartRowCap;
     float* dst = bn_part + (long long)(tile_m % cap) * 2 * N + n0;
     if (tiles_m_g > cap) {  // pre-zeroed by the caller
       for (int i = threadIdx.x; i < BN; i += blockDim.x) {

@@ -38,6 +38,7 @@
 // (reference example/distill/resnet/train_with_fleet.py conv backward via
 // Paddle; SURVEY.md §2.4 conv bwd row).
 #include "common.h"
+#include "launchers.h"
 
 using bf16 = __hip_bfloat16;
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

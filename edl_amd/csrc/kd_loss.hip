@@ -10,6 +10,7 @@
 // (C ~= 1000 classes); wave shuffle + LDS cross-wave reduction; bf16 or
 // f32 logits, f32 math.
 #include "common.h"
+#include "launchers.h"
 
 template <typename T>
 __device__ __forceinline__ float to_f32(T v);

@@ -1,0 +1,177 @@
+// The launcher ABI of the edl_amd kernel layer: every extern "C" host entry
+// point the .hip translation units define, declared exactly once.
+//
+// module.cpp (plain C++) includes this to call them; every .hip file
+// includes it too, so a definition that drifts from its declaration is a
+// compile error ("conflicting types") instead of a link that succeeds and
+// passes garbage. Host-only: nothing here but the HIP runtime API header
+// (for hipStream_t) and constants both sides must agree on.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+// Row cap of the BN-stats partial buffers the fused conv/GEMM epilogues
+// write (gemm_bt.hip, conv3x3.hip dense + small): tiles beyond the cap fold
+// atomically into row tile % cap, so the host allocates min(tiles_m, cap)
+// rows. NOT the BN kernels' own reduce grid (EDL_BN_GRID_CAP, bnrelu.hip),
+// which merely defaults to the same number.
+constexpr int kStatsPartRowCap = 192;
+
+extern "C" {
+
+// ---- fused_sgd.hip ----
+void launch_fused_sgd_f32(float* p, const float* g, float* m, float lr,
+                          float mu, float wd, float scale, long long n,
+                          const float* lr_dev, hipStream_t stream);
+
+// ---- kd_loss.hip ----
+void launch_kd_ce_fwd_f32(const float* s, const float* t, float* lpr, int B,
+                          int C, hipStream_t stream);
+void launch_kd_ce_bwd_f32(const float* s, const float* t, float* ds,
+                          float gob, int B, int C, hipStream_t stream);
+void launch_kd_ce_fwd_bf16(const void* s, const void* t, float* lpr, int B,
+                           int C, hipStream_t stream);
+void launch_kd_ce_bwd_bf16(const void* s, const void* t, void* ds, float gob,
+                           int B, int C, hipStream_t stream);
+
+// ---- softmax_ce.hip ---- (bwd: lse comes BEFORE the labels; eps, inv_B)
+void launch_softmax_ce_fwd(const void* s, int is_bf16, const long long* ya,
+                           const long long* yb, const float* lam,
+                           float* loss_row, float* lse, int* rank, float eps,
+                           int B, int C, hipStream_t stream);
+void launch_softmax_ce_bwd(const void* s, int is_bf16, const float* lse,
+                           const long long* ya, const long long* yb,
+                           const float* lam, const float* gout, void* ds,
+                           float eps, float inv_B, int B, int C,
+                           hipStream_t stream);
+
+// ---- bnrelu.hip ---- (M is long long, C int; the accumulators go
+// db_acc THEN dg_acc; the *_pad launchers take Nimg, H, W, C as ints)
+int bn_stats_grid(long long M, int C);
+int bn_bwd_grid(long long M, int C);
+void launch_bn_stats(const void* x, float* partial, int grid, long long M,
+                     int C, hipStream_t s);
+void launch_bn_finalize(float* partial, int nblocks, int zero_src,
+                        const float* gamma, const float* beta, float* mean,
+                        float* invstd, float* scale, float* shift,
+                        float* rmean, float* rvar, float momentum, float eps,
+                        long long M, int C, hipStream_t s);
+void launch_bn_apply(const void* x, const void* res, void* y,
+                     unsigned char* mask, const float* scale,
+                     const float* shift, long long M, int C, bool relu,
+                     bool add, hipStream_t s);
+void launch_bn_apply_pad(const void* x, void* yp, unsigned char* mask,
+                         const float* scale, const float* shift, int Nimg,
+                         int H, int W, int C, hipStream_t s);
+void launch_bn_bwd_reduce(const void* dy, const unsigned char* mask,
+                          const void* x, const float* mean,
+                          const float* invstd, float* partial, int grid,
+                          long long M, int C, bool relu, hipStream_t s);
+void launch_bn_bwd_finalize(const float* partial, int nblocks, float* sums,
+                            int C, float* db_acc, float* dg_acc,
+                            hipStream_t s);
+void launch_bn_bwd_dx(const void* dy, const unsigned char* mask,
+                      const void* x, const float* mean, const float* invstd,
+                      const float* gamma, const float* sums, void* dx,
+                      void* dres, long long M, int C, bool relu, bool add,
+                      bool training, hipStream_t s);
+void launch_bn_bwd_dx_pad(const void* dy, const unsigned char* mask,
+                          const void* x, const float* mean,
+                          const float* invstd, const float* gamma,
+                          const float* sums, void* dxp, int Nimg, int H,
+                          int W, int C, bool relu, hipStream_t s);
+void launch_bn_bwd_fused(const void* dy, const unsigned char* mask,
+                         const void* x, const float* mean,
+                         const float* invstd, const float* gamma,
+                         float* partial, float* sums, float* db_acc,
+                         float* dg_acc, void* dx, void* dres, int* ws,
+                         int grid, int nfin, long long M, int C, bool relu,
+                         bool add, hipStream_t s);
+
+// ---- gemm_bt.hip ---- (M, N, K: C[M,N] = A[M,K] @ B[N,K]^T)
+int gemm_bt_tiles_m(int M, int N);
+void launch_gemm_bt(const void* A, const void* B, void* C, int M, int N,
+                    int K, float* bn_part, hipStream_t s);
+void launch_gemm_bt_splitk(const void* A, const void* B, float* Cf32, int M,
+                           int N, int K, int splitk, hipStream_t s);
+
+// ---- conv3x3.hip ---- (dense/grouped take Cout BEFORE Cin, the s2 dgrad
+// Cin before Cout; HW_out, W_out, Hp, Wp, stride always in that order)
+int conv3x3_tiles_m(int M, int Cout);
+int conv3x3_small_tiles_m(int M);
+int conv3x3_pick_splitk(int M, int Cout, int Cin);
+void launch_pad_nhwc(const void* x, void* xp, int Nimg, int H, int W, int Hp,
+                     int Wp, int C, hipStream_t s);
+void launch_pad_nhwc_cpad(const void* x, void* xp, int Nimg, int H, int W,
+                          int Hp, int Wp, int Creal, int Cpad,
+                          hipStream_t s);
+void launch_conv3x3(const void* xp, const void* w3, void* y, int M, int Cout,
+                    int Cin, int HW_out, int W_out, int Hp, int Wp,
+                    int stride, float* cpart, int splitk, float* bn_part,
+                    hipStream_t s);
+void launch_conv3x3_grouped(const void* xp, const void* w3g, void* y, int M,
+                            int Cout, int Cin, int HW_out, int W_out, int Hp,
+                            int Wp, int stride, int gw, hipStream_t s);
+void launch_conv3x3_small(const void* xp, const void* w3s, void* y, int M,
+                          int Cout_real, int cpt, int HW_out, int W_out,
+                          int Hp, int Wp, int stride, float* bn_part,
+                          hipStream_t s);
+void launch_conv3x3s2_dgrad(const void* dyp, const void* wcat, void* dx,
+                            int Nimg, int H, int W, int Cin, int Cout,
+                            int Hop, int Wop, hipStream_t s);
+
+// ---- gemm_tn.hip ---- (3x3: Cout, Cin, M, then Ho, Wo, Hp, Wp; the small
+// launcher puts CinP BEFORE stride, the others end stride, splitk, perm)
+void launch_gemm_tn_splitk(const void* A, const void* B, float* C, int N1,
+                           int N2, int K, int splitk, hipStream_t s);
+void launch_gemm_tn3x3_splitk(const void* dy, const void* xpad, float* C,
+                              int Cout, int Cin, int M, int Ho, int Wo,
+                              int Hp, int Wp, int stride, int splitk,
+                              int perm, hipStream_t s);
+void launch_gemm_tn3x3_splitk_apad(const void* dyp, const void* xpad,
+                                   float* C, int Cout, int Cin, int M, int Ho,
+                                   int Wo, int Hp, int Wp, int stride,
+                                   int splitk, int perm, hipStream_t s);
+void launch_gemm_tn3x3_small(const void* dy, const void* xpad, float* C,
+                             int N1v, int N2v, int M, int Ho, int Wo, int Hp,
+                             int Wp, int CinP, int stride, int splitk,
+                             hipStream_t s);
+
+// ---- transpose.hip ---- (shift9: M, C, Mp first, then the conv geometry)
+void launch_transpose_pad(const void* in, void* out, int M, int C, int Mp,
+                          hipStream_t s);
+void launch_shift9_transpose(const void* xp, void* out, int M, int C, int Mp,
+                             int HW_out, int W_out, int Hp, int Wp,
+                             int stride, hipStream_t s);
+void launch_repack_dgrad_w3(const void* in, void* out, int Co, int Ci,
+                            int mode, hipStream_t s);
+void launch_cast_bf16_zero(float* src, void* dst, long long n, hipStream_t s);
+
+// ---- maxpool.hip ---- (input extent H, W before output extent Ho, Wo)
+void launch_maxpool3x3s2_fwd(const void* x, void* y, unsigned char* idx,
+                             int N, int H, int W, int Ho, int Wo, int C,
+                             hipStream_t s);
+void launch_maxpool3x3s2_bwd(const void* dy, const unsigned char* idx,
+                             void* dx, int N, int H, int W, int Ho, int Wo,
+                             int C, hipStream_t s);
+
+// ---- avgpool.hip ---- (as maxpool: H, W, Ho, Wo, C)
+void launch_avgpool2x2_fwd(const void* x, void* y, int N, int H, int W,
+                           int Ho, int Wo, int C, hipStream_t s);
+void launch_avgpool2x2_bwd(const void* dy, void* dx, int N, int H, int W,
+                           int Ho, int Wo, int C, hipStream_t s);
+
+// ---- dgc.hip ---- (n is long long; compact's k is unsigned, scatter's
+// long long)
+int dgc_workspace_words();
+void launch_dgc_accumulate(const float* g, float* u, float* v,
+                           const float* p, float mu, float wd, long long n,
+                           unsigned* ws, int hist_copies, hipStream_t stream);
+void launch_dgc_hist(const float* v, long long n, unsigned* ws, int pass,
+                     hipStream_t stream);
+void launch_dgc_pick(unsigned* ws, int pass, unsigned k, hipStream_t stream);
+void launch_dgc_compact(float* v, float* u, long long n, int* payload,
+                        unsigned k, unsigned* ws, hipStream_t stream);
+void launch_dgc_scatter_add(float* out, long long n, const int* payload,
+                            long long k, hipStream_t stream);
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 // window's argmax tap points back at this pixel. Both kernels stream
 // 8-channel octets with 16-B loads/stores.
 #include "common.h"
+#include "launchers.h"
 
 using bf16 = __hip_bfloat16;
 

@@ -7,125 +7,97 @@
 #include <c10/hip/HIPStream.h>
 #include <hip/hip_runtime.h>
 
-// launchers from the .hip translation units
-extern "C" void launch_fused_sgd_f32(float*, const float*, float*, float, float,
-                                     float, float, long long, const float*,
-                                     hipStream_t);
-extern "C" void launch_kd_ce_fwd_f32(const float*, const float*, float*, int, int,
-                                     hipStream_t);
-extern "C" void launch_kd_ce_bwd_f32(const float*, const float*, float*, float, int,
-                                     int, hipStream_t);
-extern "C" void launch_kd_ce_fwd_bf16(const void*, const void*, float*, int, int,
-                                      hipStream_t);
-extern "C" void launch_kd_ce_bwd_bf16(const void*, const void*, void*, float, int,
-                                      int, hipStream_t);
-extern "C" void launch_softmax_ce_fwd(const void*, int, const long long*,
-                                      const long long*, const float*, float*,
-                                      float*, int*, float, int, int,
-                                      hipStream_t);
-extern "C" void launch_softmax_ce_bwd(const void*, int, const float*,
-                                      const long long*, const long long*,
-                                      const float*, const float*, void*, float,
-                                      float, int, int, hipStream_t);
-extern "C" int bn_stats_grid(long long, int);
-extern "C" int bn_bwd_grid(long long, int);
-extern "C" void launch_bn_stats(const void*, float*, int, long long, int,
-                                hipStream_t);
-extern "C" void launch_bn_finalize(float*, int, int, const float*, const float*,
-                                   float*, float*, float*, float*, float*, float*,
-                                   float, float, long long, int, hipStream_t);
-extern "C" void launch_bn_apply(const void*, const void*, void*, unsigned char*,
-                                const float*, const float*, long long, int,
-                                bool, bool, hipStream_t);
-extern "C" void launch_bn_bwd_fused(const void*, const unsigned char*,
-                                    const void*, const float*, const float*,
-                                    const float*, float*, float*, float*,
-                                    float*, void*, void*, int*, int, int,
-                                    long long, int, bool, bool, hipStream_t);
-extern "C" void launch_bn_bwd_reduce(const void*, const unsigned char*,
-                                     const void*, const float*, const float*,
-                                     float*, int, long long, int, bool,
-                                     hipStream_t);
-extern "C" void launch_bn_bwd_finalize(const float*, int, float*, int, float*,
-                                       float*, hipStream_t);
-extern "C" void launch_gemm_bt(const void*, const void*, void*, int, int, int,
-                               float*, hipStream_t);
-extern "C" int gemm_bt_tiles_m(int, int);
-extern "C" int conv3x3_tiles_m(int, int);
-extern "C" void launch_pad_nhwc(const void*, void*, int, int, int, int, int, int,
-                                hipStream_t);
-extern "C" void launch_conv3x3(const void*, const void*, void*, int, int, int,
-                               int, int, int, int, int, float*, int, float*,
-                               hipStream_t);
-extern "C" int conv3x3_pick_splitk(int, int, int);
-extern "C" void launch_conv3x3_grouped(const void*, const void*, void*, int, int,
-                                       int, int, int, int, int, int, int,
-                                       hipStream_t);
-extern "C" void launch_conv3x3s2_dgrad(const void*, const void*, void*, int,
-                                       int, int, int, int, int, int,
-                                       hipStream_t);
-extern "C" void launch_conv3x3_small(const void*, const void*, void*, int, int,
-                                     int, int, int, int, int, int, float*,
-                                     hipStream_t);
-extern "C" void launch_gemm_tn3x3_small(const void*, const void*, float*,
-                                        int, int, int, int, int, int, int,
-                                        int, int, int, hipStream_t);
-extern "C" void launch_pad_nhwc_cpad(const void*, void*, int, int, int, int,
-                                     int, int, int, hipStream_t);
-extern "C" void launch_cast_bf16_zero(float*, void*, long long, hipStream_t);
-extern "C" void launch_repack_dgrad_w3(const void*, void*, int, int, int,
-                                       hipStream_t);
-extern "C" void launch_maxpool3x3s2_fwd(const void*, void*, unsigned char*,
-                                        int, int, int, int, int, int,
-                                        hipStream_t);
-extern "C" void launch_maxpool3x3s2_bwd(const void*, const unsigned char*,
-                                        void*, int, int, int, int, int, int,
-                                        hipStream_t);
-extern "C" void launch_transpose_pad(const void*, void*, int, int, int,
-                                     hipStream_t);
-extern "C" void launch_gemm_bt_splitk(const void*, const void*, float*, int, int,
-                                      int, int, hipStream_t);
-extern "C" void launch_shift9_transpose(const void*, void*, int, int, int, int,
-                                        int, int, int, int, hipStream_t);
-extern "C" void launch_gemm_tn_splitk(const void*, const void*, float*, int,
-                                      int, int, int, hipStream_t);
-extern "C" void launch_gemm_tn3x3_splitk(const void*, const void*, float*, int,
-                                         int, int, int, int, int, int, int,
-                                         int, int, hipStream_t);
-extern "C" void launch_avgpool2x2_fwd(const void*, void*, int, int, int, int,
-                                      int, int, hipStream_t);
-extern "C" void launch_avgpool2x2_bwd(const void*, void*, int, int, int, int,
-                                      int, int, hipStream_t);
-extern "C" void launch_bn_bwd_dx(const void*, const unsigned char*, const void*,
-                                 const float*, const float*, const float*,
-                                 const float*, void*, void*, long long, int,
-                                 bool, bool, bool, hipStream_t);
-extern "C" void launch_bn_apply_pad(const void*, void*, unsigned char*,
-                                    const float*, const float*, int, int, int,
-                                    int, hipStream_t);
-extern "C" void launch_bn_bwd_dx_pad(const void*, const unsigned char*,
-                                     const void*, const float*, const float*,
-                                     const float*, const float*, void*, int,
-                                     int, int, int, bool, hipStream_t);
-extern "C" void launch_gemm_tn3x3_splitk_apad(const void*, const void*, float*,
-                                              int, int, int, int, int, int,
-                                              int, int, int, int, hipStream_t);
-extern "C" int dgc_workspace_words();
-extern "C" void launch_dgc_accumulate(const float*, float*, float*,
-                                      const float*, float, float, long long,
-                                      unsigned*, int, hipStream_t);
-extern "C" void launch_dgc_hist(const float*, long long, unsigned*, int,
-                                hipStream_t);
-extern "C" void launch_dgc_pick(unsigned*, int, unsigned, hipStream_t);
-extern "C" void launch_dgc_compact(float*, float*, long long, int*, unsigned,
-                                   unsigned*, hipStream_t);
-extern "C" void launch_dgc_scatter_add(float*, long long, const int*,
-                                       long long, hipStream_t);
+#include "launchers.h"  // every launcher of the .hip translation units
 
 namespace {
 
 hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
+}
+
+// ---- checks and arithmetic the bindings share ----------------------------
+
+// x must be a 4-D channels_last bf16 GPU tensor; cmod > 0 additionally
+// requires C % cmod == 0 (sites that check no modulus pass none)
+void check_nhwc_bf16(const torch::Tensor& x, const char* who, int cmod = 0) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
+                  x.scalar_type() == torch::kBFloat16 &&
+                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
+              who, ": 4-D channels_last bf16 GPU tensor required");
+  TORCH_CHECK(cmod <= 0 || x.size(1) % cmod == 0, who, ": C % ", cmod);
+}
+
+// output extent of a 3x3 pad-1 conv (or ceil-mode stride-2 pool)
+int out_extent(int64_t in, int64_t stride) {
+  return (int)((in - 1) / stride + 1);
+}
+
+// split-K pick: total blocks ~ 2x CUs, at most `upper` k-slices
+int64_t auto_splitk(int tiles, int64_t upper) {
+  const int64_t sk = std::max<int64_t>(1, 512 / std::max(1, tiles));
+  return std::min(sk, upper);
+}
+
+// a [M, K] and b [N, K]: 2-D bf16 GPU operands of a bt GEMM, K, N % 64
+void check_bt_operands(const torch::Tensor& a, const torch::Tensor& b,
+                       const char* who) {
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dim() == 2 && b.dim() == 2 &&
+                  a.size(1) == b.size(1),
+              who, ": [M,K] x [N,K] GPU tensors required");
+  TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
+                  b.scalar_type() == torch::kBFloat16,
+              who, ": bf16 only");
+  TORCH_CHECK(a.size(1) % 64 == 0 && b.size(0) % 64 == 0, who,
+              ": K,N % 64 == 0");
+}
+
+// n-tiles of the TN kernels along one output dim (n % 64 == 0)
+int tn_tiles(int n) { return n / (n % 128 == 0 ? 128 : 64); }
+
+// wgrad target: the caller's fp32 buffer of rows*cols elements to
+// ACCUMULATE into (direct-grad mode: the param's bucket-view gradient,
+// pre-zeroed by reducer.zero_grad — no fresh zeros tensor, no
+// AccumulateGrad add afterwards), else fresh zeros [rows, cols]
+torch::Tensor out_or_zeros(const c10::optional<torch::Tensor>& out,
+                           int64_t rows, int64_t cols,
+                           torch::TensorOptions opts, const char* msg) {
+  if (!out.has_value())
+    return torch::zeros({rows, cols}, opts.dtype(torch::kFloat32));
+  TORCH_CHECK(out->is_contiguous() &&
+                  out->scalar_type() == torch::kFloat32 &&
+                  out->numel() == rows * cols,
+              msg);
+  return *out;
+}
+
+// optional fp32 [C] accumulator (direct-grad mode) -> pointer or null
+float* acc_ptr(const c10::optional<torch::Tensor>& acc, int64_t C,
+               const char* msg) {
+  if (!acc.has_value()) return nullptr;
+  TORCH_CHECK(acc->numel() == C && acc->is_contiguous() &&
+                  acc->scalar_type() == torch::kFloat32,
+              msg);
+  return acc->data_ptr<float>();
+}
+
+// pad_hw = (H, W) of the [M, C] rows' images -> (N, H, W) of the zero-halo
+// padded buffer [N, H+2, W+2, C]
+struct PadNHW {
+  int64_t n = 0, h = 0, w = 0;
+};
+
+PadNHW parse_pad_hw(const std::vector<int64_t>& pad_hw, long long M,
+                    const char* who) {
+  TORCH_CHECK(pad_hw.size() == 2, who, ": pad_hw = (H, W)");
+  PadNHW p;
+  p.h = pad_hw[0];
+  p.w = pad_hw[1];
+  TORCH_CHECK(p.h >= 1 && p.w >= 1 && M >= 1 && M % (p.h * p.w) == 0, who,
+              ": pad_hw does not divide the rows of x");
+  p.n = M / (p.h * p.w);
+  TORCH_CHECK(p.n * (p.h + 2) * (p.w + 2) < (1LL << 31), who,
+              ": padded pixel count must stay below 2^31");
+  return p;
 }
 
 // ---- DGC top-k compress / decode (dgc.hip) -------------------------------
@@ -388,6 +360,17 @@ static torch::Tensor part_pool_get(int rows, int64_t cols,
   return t;
 }
 
+// fp32 [min(tiles_m, cap), cols] stats-partial buffer for a fused epilogue:
+// capped (atomically folded) partials come from the pre-zeroed pool, the
+// rest are written once per row and can be transient
+torch::Tensor stats_part_buf(int tiles_m, int64_t cols,
+                             torch::TensorOptions opts) {
+  opts = opts.dtype(torch::kFloat32);
+  const int rows = std::min(tiles_m, kStatsPartRowCap);
+  return tiles_m > rows ? part_pool_get(rows, cols, opts)
+                        : torch::empty({rows, cols}, opts);
+}
+
 // x: NHWC bf16 viewed as [M, C] contiguous (channels_last 4-D collapses to
 // this). gamma/beta/running stats: fp32 [C].
 void check_bn_inputs_eval(const torch::Tensor& x, int64_t C) {
@@ -420,18 +403,11 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
               "bn: x must be a contiguous [M, C] view");
   check_bn_inputs(x, C);
   const long long M = x.numel() / C;
-  int64_t pad_n = 0, pad_h = 0, pad_w = 0;
+  PadNHW pad;  // pad.n == 0: plain [M, C] output
   if (pad_hw.has_value()) {
-    TORCH_CHECK(pad_hw->size() == 2, "bn: pad_hw = (H, W)");
-    pad_h = (*pad_hw)[0];
-    pad_w = (*pad_hw)[1];
     TORCH_CHECK(relu && !res.has_value(),
                 "bn: pad_hw needs relu and no residual");
-    TORCH_CHECK(pad_h >= 1 && pad_w >= 1 && M >= 1 && M % (pad_h * pad_w) == 0,
-                "bn: pad_hw does not divide the rows of x");
-    pad_n = M / (pad_h * pad_w);
-    TORCH_CHECK(pad_n * (pad_h + 2) * (pad_w + 2) < (1LL << 31),
-                "bn: padded pixel count must stay below 2^31");
+    pad = parse_pad_hw(*pad_hw, M, "bn");
   }
   auto opts = gamma.options().dtype(torch::kFloat32);
   const int grid = bn_stats_grid(M, (int)C);
@@ -440,7 +416,7 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
   auto invstd = torch::empty({C}, opts);
   auto scale = torch::empty({C}, opts);
   auto shift = torch::empty({C}, opts);
-  auto y = pad_n ? torch::empty({pad_n, pad_h + 2, pad_w + 2, C}, x.options())
+  auto y = pad.n ? torch::empty({pad.n, pad.h + 2, pad.w + 2, C}, x.options())
                  : torch::empty_like(x);
   // 1-bit/channel ReLU mask for the backward (one byte per channel octet)
   auto msk = relu ? torch::empty({M, C / 8}, x.options().dtype(torch::kUInt8))
@@ -474,18 +450,18 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
                      rmean.defined() ? rmean.data_ptr<float>() : nullptr,
                      rvar.defined() ? rvar.data_ptr<float>() : nullptr,
                      (float)momentum, (float)eps, M, (int)C, s);
-  if (pad_n) {
+  if (pad.n) {
     launch_bn_apply_pad(x.data_ptr(), y.data_ptr(),
                         (unsigned char*)msk.data_ptr(),
                         scale.data_ptr<float>(), shift.data_ptr<float>(),
-                        (int)pad_n, (int)pad_h, (int)pad_w, (int)C, s);
-    return {y, mean, invstd, msk};
+                        (int)pad.n, (int)pad.h, (int)pad.w, (int)C, s);
+  } else {
+    launch_bn_apply(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr,
+                    y.data_ptr(),
+                    relu ? (unsigned char*)msk.data_ptr() : nullptr,
+                    scale.data_ptr<float>(), shift.data_ptr<float>(), M,
+                    (int)C, relu, res.has_value(), s);
   }
-  launch_bn_apply(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr,
-                  y.data_ptr(),
-                  relu ? (unsigned char*)msk.data_ptr() : nullptr,
-                  scale.data_ptr<float>(), shift.data_ptr<float>(),
-                  M, (int)C, relu, res.has_value(), s);
   return {y, mean, invstd, msk};
 }
 
@@ -523,19 +499,12 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
   // read per call (not static) so tests can A/B via os.environ
   const char* fenv = getenv("EDL_BN_BWD_FUSED");
   const bool fused_bwd = fenv ? atoi(fenv) != 0 : false;
-  int64_t pad_n = 0, pad_h = 0, pad_w = 0;
+  PadNHW pad;  // pad.n == 0: plain [M, C] dx
   if (pad_hw.has_value() && !(fused_bwd && training)) {
-    TORCH_CHECK(pad_hw->size() == 2, "bn_bwd: pad_hw = (H, W)");
-    pad_h = (*pad_hw)[0];
-    pad_w = (*pad_hw)[1];
     TORCH_CHECK(training && !add, "bn_bwd: pad_hw needs training, no residual");
-    TORCH_CHECK(pad_h >= 1 && pad_w >= 1 && M >= 1 && M % (pad_h * pad_w) == 0,
-                "bn_bwd: pad_hw does not divide the rows of x");
-    pad_n = M / (pad_h * pad_w);
-    TORCH_CHECK(pad_n * (pad_h + 2) * (pad_w + 2) < (1LL << 31),
-                "bn_bwd: padded pixel count must stay below 2^31");
+    pad = parse_pad_hw(*pad_hw, M, "bn_bwd");
   }
-  auto dx = pad_n ? torch::empty({pad_n, pad_h + 2, pad_w + 2, C}, x.options())
+  auto dx = pad.n ? torch::empty({pad.n, pad.h + 2, pad.w + 2, C}, x.options())
                   : torch::empty_like(x);
   auto dres = add ? torch::empty_like(x) : torch::Tensor();
   auto s = cur_stream();
@@ -546,20 +515,8 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
       relu ? (const unsigned char*)msk->data_ptr() : nullptr;
   // direct-grad mode: accumulate dgamma/dbeta straight into the params'
   // bucket-view gradients (skips the per-param AccumulateGrad kernels)
-  float* dg_acc = nullptr;
-  float* db_acc = nullptr;
-  if (dgamma_acc.has_value()) {
-    TORCH_CHECK(dgamma_acc->numel() == C && dgamma_acc->is_contiguous() &&
-                    dgamma_acc->scalar_type() == torch::kFloat32,
-                "bn_bwd: dgamma_acc fp32 [C]");
-    dg_acc = dgamma_acc->data_ptr<float>();
-  }
-  if (dbeta_acc.has_value()) {
-    TORCH_CHECK(dbeta_acc->numel() == C && dbeta_acc->is_contiguous() &&
-                    dbeta_acc->scalar_type() == torch::kFloat32,
-                "bn_bwd: dbeta_acc fp32 [C]");
-    db_acc = dbeta_acc->data_ptr<float>();
-  }
+  float* dg_acc = acc_ptr(dgamma_acc, C, "bn_bwd: dgamma_acc fp32 [C]");
+  float* db_acc = acc_ptr(dbeta_acc, C, "bn_bwd: dbeta_acc fp32 [C]");
   if (fused_bwd && training) {
     // one launch: reduce + last-block finalize + dx (grid-wide flag sync);
     // ws = persistent per-device {arrive, flag, depart} ints, self-resetting
@@ -597,66 +554,64 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
                        partial.data_ptr<float>(), grid, M, (int)C, relu, s);
   launch_bn_bwd_finalize(partial.data_ptr<float>(), grid, sums.data_ptr<float>(),
                          (int)C, db_acc, dg_acc, s);
-  if (pad_n) {
+  if (pad.n) {
     launch_bn_bwd_dx_pad(dyc.data_ptr(), mp, x.data_ptr(),
                          mean.data_ptr<float>(), invstd.data_ptr<float>(),
                          gamma.data_ptr<float>(), sums.data_ptr<float>(),
-                         dx.data_ptr(), (int)pad_n, (int)pad_h, (int)pad_w,
+                         dx.data_ptr(), (int)pad.n, (int)pad.h, (int)pad.w,
                          (int)C, relu, s);
-    return {dx, sums[1], sums[0], dres};
+  } else {
+    launch_bn_bwd_dx(dyc.data_ptr(), mp, x.data_ptr(), mean.data_ptr<float>(),
+                     invstd.data_ptr<float>(), gamma.data_ptr<float>(),
+                     sums.data_ptr<float>(), dx.data_ptr(),
+                     add ? dres.data_ptr() : nullptr, M, (int)C, relu, add,
+                     training, s);
   }
-  launch_bn_bwd_dx(dyc.data_ptr(), mp, x.data_ptr(),
-                   mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                   gamma.data_ptr<float>(), sums.data_ptr<float>(), dx.data_ptr(),
-                   add ? dres.data_ptr() : nullptr, M, (int)C, relu, add, training,
-                   s);
   // dbeta = sums[0], dgamma = sums[1] (views of the reduce workspace)
   return {dx, sums[1], sums[0], dres};
 }
 
-torch::Tensor gemm_bt(torch::Tensor a, torch::Tensor b) {
-  // C[M, N] = A[M, K] @ B[N, K]^T, bf16 row-major
-  TORCH_CHECK(a.is_cuda() && b.is_cuda(), "gemm_bt: GPU tensors required");
-  TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
-                  b.scalar_type() == torch::kBFloat16,
-              "gemm_bt: bf16 only");
-  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1),
-              "gemm_bt: [M,K] x [N,K]");
+// C[M, N] = A[M, K] @ B[N, K]^T, bf16 row-major -> {C} or, with_stats,
+// {C, BN stats partials [tiles_m, 2N] of the bf16-rounded output} (the
+// following BN skips its stats kernel)
+std::vector<torch::Tensor> gemm_bt_impl(const torch::Tensor& a,
+                                        const torch::Tensor& b,
+                                        bool with_stats) {
+  check_bt_operands(a, b, "gemm_bt");
   auto ac = a.contiguous();
   auto bc = b.contiguous();
   const int M = (int)a.size(0), K = (int)a.size(1), N = (int)b.size(0);
-  TORCH_CHECK(K % 64 == 0 && N % 64 == 0, "gemm_bt: K,N % 64 == 0");
   auto c = torch::empty({M, N}, a.options());
-  launch_gemm_bt(ac.data_ptr(), bc.data_ptr(), c.data_ptr(), M, N, K, nullptr,
-                 cur_stream());
-  return c;
+  torch::Tensor part;
+  if (with_stats)
+    part = stats_part_buf(gemm_bt_tiles_m(M, N), 2 * N, a.options());
+  launch_gemm_bt(ac.data_ptr(), bc.data_ptr(), c.data_ptr(), M, N, K,
+                 with_stats ? part.data_ptr<float>() : nullptr, cur_stream());
+  return {c, part};  // part undefined without stats
 }
 
+torch::Tensor gemm_bt(torch::Tensor a, torch::Tensor b) {
+  return gemm_bt_impl(a, b, false)[0];
+}
 
 std::vector<torch::Tensor> gemm_bt_stats(torch::Tensor a, torch::Tensor b) {
-  // like gemm_bt, additionally returning BN stats partials [tiles_m, 2N]
-  // of the bf16-rounded output (the following BN skips its stats kernel)
-  TORCH_CHECK(a.is_cuda() && b.is_cuda(), "gemm_bt: GPU tensors required");
-  TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
-                  b.scalar_type() == torch::kBFloat16,
-              "gemm_bt: bf16 only");
-  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && a.size(1) == b.size(1),
-              "gemm_bt: [M,K] x [N,K]");
-  auto ac = a.contiguous();
-  auto bc = b.contiguous();
-  const int M = (int)a.size(0), K = (int)a.size(1), N = (int)b.size(0);
-  TORCH_CHECK(K % 64 == 0 && N % 64 == 0, "gemm_bt: K,N % 64 == 0");
-  auto c = torch::empty({M, N}, a.options());
-  const int tiles_m = gemm_bt_tiles_m(M, N);
-  const int rows = std::min(tiles_m, 192);
-  auto part = tiles_m > rows
-                  ? part_pool_get(rows, 2 * N,
-                                  a.options().dtype(torch::kFloat32))
-                  : torch::empty({rows, 2 * N},
-                                 a.options().dtype(torch::kFloat32));
-  launch_gemm_bt(ac.data_ptr(), bc.data_ptr(), c.data_ptr(), M, N, K,
-                 part.data_ptr<float>(), cur_stream());
-  return {c, part};
+  return gemm_bt_impl(a, b, true);
+}
+
+// flat zero-halo padded copy of x [N, C, H, W] channels_last bf16, widened
+// to cpad >= C channels: N * (H+2) * (W+2) * cpad elements
+torch::Tensor pad_nhwc_flat(const torch::Tensor& x, int cpad, hipStream_t s) {
+  const int Nimg = (int)x.size(0), C = (int)x.size(1);
+  const int H = (int)x.size(2), W = (int)x.size(3);
+  const int Hp = H + 2, Wp = W + 2;
+  auto xp = torch::empty({(long long)Nimg * Hp * Wp * cpad}, x.options());
+  if (C == cpad) {
+    launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, C, s);
+  } else {
+    launch_pad_nhwc_cpad(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, C,
+                         cpad, s);
+  }
+  return xp;
 }
 
 torch::Tensor conv3x3_grouped_fwd(torch::Tensor x, torch::Tensor w3g,
@@ -664,10 +619,7 @@ torch::Tensor conv3x3_grouped_fwd(torch::Tensor x, torch::Tensor w3g,
   // grouped 3x3: w3g [Cout, 9*gw] where gw = the gemm group width —
   // channels-per-group when >= 64 (exact, zero wasted MFMA), else 64
   // with a block-diagonal zero-padded repack (conv.py _repack_w3_grouped)
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "conv3x3g: 4-D channels_last bf16");
+  check_nhwc_bf16(x, "conv3x3g");
   const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
   const int Cout = (int)w3g.size(0);
@@ -676,30 +628,27 @@ torch::Tensor conv3x3_grouped_fwd(torch::Tensor x, torch::Tensor w3g,
   TORCH_CHECK(gw % 64 == 0 && Cin % gw == 0, "conv3x3g: gw % 64, Cin % gw");
   TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0 && Cin == Cout,
               "conv3x3g: C % 64, equal in/out");
-  const int Hp = H + 2, Wp = W + 2;
-  const int Hout = (H + 2 - 3) / (int)stride + 1;
-  const int Wout = (W + 2 - 3) / (int)stride + 1;
+  const int Hout = out_extent(H, stride), Wout = out_extent(W, stride);
   const long long M = (long long)Nimg * Hout * Wout;
   auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * Cin}, x.options());
-  launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
+  auto xp = pad_nhwc_flat(x, Cin, s);
   auto y = torch::empty({M, Cout}, x.options());
   launch_conv3x3_grouped(xp.data_ptr(), w3g.data_ptr(), y.data_ptr(), (int)M,
-                         Cout, Cin, Hout * Wout, Wout, Hp, Wp, (int)stride,
-                         gw, s);
+                         Cout, Cin, Hout * Wout, Wout, H + 2, W + 2,
+                         (int)stride, gw, s);
   return y;
 }
 
-torch::Tensor conv3x3_small_fwd(torch::Tensor x, torch::Tensor w3s,
-                                int64_t cout_real, int64_t cpt,
-                                int64_t stride) {
-  // stem conv (small channels): x [N, Cin, H, W] channels_last bf16 with
-  // Cin <= cpt (cpt in {16,32,64}); w3s [64, TAPS_PAD*cpt] zero-padded
-  // repack (conv.py _repack_w3_small). Returns y2d [M, cout_real].
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "conv3x3s: 4-D channels_last bf16");
+// stem conv (small channels): x [N, Cin, H, W] channels_last bf16 with
+// Cin <= cpt (cpt in {16,32,64}); w3s [64, TAPS_PAD*cpt] zero-padded
+// repack (conv.py _repack_w3_small). Returns {y2d [M, cout_real]} or,
+// with_stats, {y2d, BN stats partials [tiles_m, 2*cout_real]}.
+std::vector<torch::Tensor> conv3x3_small_impl(const torch::Tensor& x,
+                                              const torch::Tensor& w3s,
+                                              int64_t cout_real, int64_t cpt,
+                                              int64_t stride,
+                                              bool with_stats) {
+  check_nhwc_bf16(x, "conv3x3s");
   TORCH_CHECK(stride == 1 || stride == 2, "conv3x3s: stride 1 or 2");
   TORCH_CHECK(cpt == 16 || cpt == 32 || cpt == 64, "conv3x3s: cpt 16/32/64");
   const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
@@ -710,23 +659,26 @@ torch::Tensor conv3x3_small_fwd(torch::Tensor x, torch::Tensor w3s,
                   w3s.size(1) == taps_pad * cpt,
               "conv3x3s: w3s [64, taps_pad*cpt]");
   TORCH_CHECK(cout_real >= 1 && cout_real <= 64, "conv3x3s: cout <= 64");
-  const int Hp = H + 2, Wp = W + 2;
-  const int Hout = (H - 1) / (int)stride + 1;
-  const int Wout = (W - 1) / (int)stride + 1;
+  const int Hout = out_extent(H, stride), Wout = out_extent(W, stride);
   const long long M = (long long)Nimg * Hout * Wout;
   auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * cpt}, x.options());
-  if (Cin == cpt) {
-    launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
-  } else {
-    launch_pad_nhwc_cpad(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp,
-                         Cin, (int)cpt, s);
-  }
+  auto xp = pad_nhwc_flat(x, (int)cpt, s);
   auto y = torch::empty({M, cout_real}, x.options());
+  torch::Tensor bpart;
+  if (with_stats)
+    bpart = stats_part_buf(conv3x3_small_tiles_m((int)M), 2 * cout_real,
+                           x.options());
   launch_conv3x3_small(xp.data_ptr(), w3s.data_ptr(), y.data_ptr(), (int)M,
-                       (int)cout_real, (int)cpt, Hout * Wout, Wout, Hp, Wp,
-                       (int)stride, nullptr, s);
-  return y;
+                       (int)cout_real, (int)cpt, Hout * Wout, Wout, H + 2,
+                       W + 2, (int)stride,
+                       with_stats ? bpart.data_ptr<float>() : nullptr, s);
+  return {y, bpart};  // bpart undefined without stats
+}
+
+torch::Tensor conv3x3_small_fwd(torch::Tensor x, torch::Tensor w3s,
+                                int64_t cout_real, int64_t cpt,
+                                int64_t stride) {
+  return conv3x3_small_impl(x, w3s, cout_real, cpt, stride, false)[0];
 }
 
 std::vector<torch::Tensor> conv3x3_small_fwd_stats(torch::Tensor x,
@@ -734,45 +686,7 @@ std::vector<torch::Tensor> conv3x3_small_fwd_stats(torch::Tensor x,
                                                    int64_t cout_real,
                                                    int64_t cpt,
                                                    int64_t stride) {
-  // conv3x3_small_fwd + BN stats partials [tiles_m, 2*cout_real]
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "conv3x3s: 4-D channels_last bf16");
-  TORCH_CHECK(stride == 1 || stride == 2, "conv3x3s: stride 1 or 2");
-  TORCH_CHECK(cpt == 16 || cpt == 32 || cpt == 64, "conv3x3s: cpt 16/32/64");
-  const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
-  TORCH_CHECK(Cin <= cpt, "conv3x3s: Cin <= cpt");
-  const int taps_pad = cpt == 16 ? 12 : (cpt == 32 ? 10 : 9);
-  TORCH_CHECK(w3s.is_contiguous() && w3s.size(0) == 64 &&
-                  w3s.size(1) == taps_pad * cpt,
-              "conv3x3s: w3s [64, taps_pad*cpt]");
-  TORCH_CHECK(cout_real >= 1 && cout_real <= 64, "conv3x3s: cout <= 64");
-  const int Hp = H + 2, Wp = W + 2;
-  const int Hout = (H - 1) / (int)stride + 1;
-  const int Wout = (W - 1) / (int)stride + 1;
-  const long long M = (long long)Nimg * Hout * Wout;
-  auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * cpt}, x.options());
-  if (Cin == cpt) {
-    launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
-  } else {
-    launch_pad_nhwc_cpad(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp,
-                         Cin, (int)cpt, s);
-  }
-  auto y = torch::empty({M, cout_real}, x.options());
-  const int tiles_m = (int)((M + 255) / 256);
-  const int rows = std::min(tiles_m, 192);
-  auto bpart = tiles_m > rows
-                   ? part_pool_get(rows, 2 * cout_real,
-                                   x.options().dtype(torch::kFloat32))
-                   : torch::empty({rows, 2 * cout_real},
-                                  x.options().dtype(torch::kFloat32));
-  launch_conv3x3_small(xp.data_ptr(), w3s.data_ptr(), y.data_ptr(), (int)M,
-                       (int)cout_real, (int)cpt, Hout * Wout, Wout, Hp, Wp,
-                       (int)stride, bpart.data_ptr<float>(), s);
-  return {y, bpart};
+  return conv3x3_small_impl(x, w3s, cout_real, cpt, stride, true);
 }
 
 // ---- zero-halo padded NHWC buffers -------------------------------------
@@ -784,13 +698,9 @@ std::vector<torch::Tensor> conv3x3_small_fwd_stats(torch::Tensor x,
 
 // x: 4-D channels_last bf16 -> xp [N, H+2, W+2, C]
 torch::Tensor pad_nhwc(torch::Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "pad_nhwc: 4-D channels_last bf16");
+  check_nhwc_bf16(x, "pad_nhwc", 8);
   const int Nimg = (int)x.size(0), C = (int)x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
-  TORCH_CHECK(C % 8 == 0, "pad_nhwc: C % 8");
   auto xp = torch::empty({Nimg, H + 2, W + 2, C}, x.options());
   launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, H + 2, W + 2, C,
                   cur_stream());
@@ -828,13 +738,9 @@ torch::Tensor conv3x3s2_dgrad_padded(torch::Tensor dyp, torch::Tensor wcat,
 torch::Tensor conv3x3s2_dgrad(torch::Tensor dy, torch::Tensor wcat,
                               int64_t H, int64_t W) {
   // dy: [N, Cout, Ho, Wo] channels_last bf16 (pads, then the call above)
-  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
-                  dy.scalar_type() == torch::kBFloat16 &&
-                  dy.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "s2dgrad: 4-D channels_last bf16 dy");
+  check_nhwc_bf16(dy, "s2dgrad dy", 64);
   TORCH_CHECK((H + 1) / 2 == dy.size(2) && (W + 1) / 2 == dy.size(3),
               "s2dgrad: shape");
-  TORCH_CHECK(dy.size(1) % 64 == 0, "s2dgrad: C % 64");
   return conv3x3s2_dgrad_padded(pad_nhwc(dy), wcat, H, W);
 }
 
@@ -857,13 +763,9 @@ torch::Tensor repack_dgrad_w3(torch::Tensor w_smaj, int64_t ci,
 }
 
 std::vector<torch::Tensor> maxpool3x3s2_fwd(torch::Tensor x) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "maxpool3x3s2: 4-D channels_last bf16");
+  check_nhwc_bf16(x, "maxpool3x3s2", 8);
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
-  TORCH_CHECK(C % 8 == 0, "maxpool3x3s2: C % 8");
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   auto y = torch::empty({N, C, Ho, Wo},
                         x.options().memory_format(torch::MemoryFormat::ChannelsLast));
@@ -877,10 +779,7 @@ std::vector<torch::Tensor> maxpool3x3s2_fwd(torch::Tensor x) {
 
 torch::Tensor maxpool3x3s2_bwd(torch::Tensor dy, torch::Tensor idx,
                                int64_t H, int64_t W) {
-  TORCH_CHECK(dy.is_cuda() && dy.dim() == 4 &&
-                  dy.scalar_type() == torch::kBFloat16 &&
-                  dy.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "maxpool3x3s2_bwd: 4-D channels_last bf16");
+  check_nhwc_bf16(dy, "maxpool3x3s2_bwd");  // idx is taken on trust
   const int N = (int)dy.size(0), C = (int)dy.size(1);
   const int Ho = (int)dy.size(2), Wo = (int)dy.size(3);
   auto dx = torch::empty({N, C, (long long)H, (long long)W},
@@ -893,13 +792,9 @@ torch::Tensor maxpool3x3s2_bwd(torch::Tensor dy, torch::Tensor idx,
 
 torch::Tensor avgpool2x2_fwd(torch::Tensor x) {
   // x: 4-D channels_last bf16; 2x2 stride-2 ceil_mode pool
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "avgpool2x2: 4-D channels_last bf16");
+  check_nhwc_bf16(x, "avgpool2x2", 8);
   const int N = (int)x.size(0), C = (int)x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
-  TORCH_CHECK(C % 8 == 0, "avgpool2x2: C % 8");
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   auto y = torch::empty({N, C, Ho, Wo},
                         x.options().memory_format(torch::MemoryFormat::ChannelsLast));
@@ -927,8 +822,7 @@ torch::Tensor conv3x3_wgrad_operand_padded(torch::Tensor xp, int64_t H,
   TORCH_CHECK(stride == 1 || stride == 2, "wgrad_operand: stride 1 or 2");
   const int Nimg = (int)xp.size(0), Cin = (int)xp.size(3);
   const int Hp = (int)H + 2, Wp = (int)W + 2;
-  const int Hout = ((int)H - 1) / (int)stride + 1;
-  const int Wout = ((int)W - 1) / (int)stride + 1;
+  const int Hout = out_extent(H, stride), Wout = out_extent(W, stride);
   const int M = Nimg * Hout * Wout;
   const int Mp = (M + 63) / 64 * 64;
   auto out = torch::empty({(long long)9 * Cin, Mp}, xp.options());
@@ -946,21 +840,14 @@ torch::Tensor conv3x3_wgrad_operand(torch::Tensor x, int64_t stride) {
 
 torch::Tensor gemm_bt_splitk(torch::Tensor a, torch::Tensor b, int64_t splitk) {
   // fp32 C[M,N] = A[M,K] @ B[N,K]^T with grid.y k-slices (atomic combine).
-  TORCH_CHECK(a.is_cuda() && b.is_cuda() && a.dim() == 2 && b.dim() == 2 &&
-                  a.size(1) == b.size(1),
-              "gemm_bt_splitk: [M,K] x [N,K] GPU");
-  TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
-                  b.scalar_type() == torch::kBFloat16,
-              "gemm_bt_splitk: bf16 only");
+  check_bt_operands(a, b, "gemm_bt_splitk");
   auto ac = a.contiguous();
   auto bc = b.contiguous();
   const int M = (int)a.size(0), K = (int)a.size(1), N = (int)b.size(0);
-  TORCH_CHECK(K % 64 == 0 && N % 64 == 0, "gemm_bt_splitk: K,N % 64");
   if (splitk <= 0) {
     // pick splitk so total blocks ~ 2x CUs, bounded by k-tiles
     const int tiles = ((M + 127) / 128) * ((N + 63) / 64);
-    splitk = std::max<int64_t>(1, 512 / std::max(1, tiles));
-    splitk = std::min<int64_t>(splitk, K / 64);
+    splitk = auto_splitk(tiles, K / 64);
   }
   auto c = torch::zeros({M, N}, a.options().dtype(torch::kFloat32));
   launch_gemm_bt_splitk(ac.data_ptr(), bc.data_ptr(), c.data_ptr<float>(), M, N,
@@ -983,24 +870,10 @@ torch::Tensor gemm_tn_splitk(torch::Tensor a, torch::Tensor b, int64_t splitk,
   const int K = (int)a.size(0), N1 = (int)a.size(1), N2 = (int)b.size(1);
   TORCH_CHECK(N1 % 64 == 0 && N2 % 64 == 0, "gemm_tn_splitk: N1,N2 % 64");
   const int nchunks = (K + 63) / 64;
-  if (splitk <= 0) {
-    const int tiles = (N1 / (N1 % 128 == 0 ? 128 : 64)) *
-                      (N2 / (N2 % 128 == 0 ? 128 : 64));
-    splitk = std::max<int64_t>(1, 512 / std::max(1, tiles));
-  }
+  if (splitk <= 0) splitk = auto_splitk(tn_tiles(N1) * tn_tiles(N2), nchunks);
   splitk = std::min<int64_t>(splitk, nchunks);
-  torch::Tensor c;
-  if (out.has_value()) {
-    // direct-grad mode: ACCUMULATE into the caller's fp32 buffer (the
-    // param's bucket-view gradient, pre-zeroed by reducer.zero_grad) —
-    // no fresh zeros tensor, no AccumulateGrad add afterwards
-    c = *out;
-    TORCH_CHECK(c.is_contiguous() && c.scalar_type() == torch::kFloat32 &&
-                    c.numel() == (int64_t)N1 * N2,
-                "gemm_tn_splitk: out fp32 contiguous [N1,N2]");
-  } else {
-    c = torch::zeros({N1, N2}, a.options().dtype(torch::kFloat32));
-  }
+  auto c = out_or_zeros(out, N1, N2, a.options(),
+                        "gemm_tn_splitk: out fp32 contiguous [N1,N2]");
   launch_gemm_tn_splitk(ac.data_ptr(), bc.data_ptr(), c.data_ptr<float>(), N1,
                         N2, K, (int)splitk, cur_stream());
   return c;
@@ -1025,7 +898,7 @@ torch::Tensor gemm_tn3x3_splitk_padded(torch::Tensor dy, torch::Tensor xp,
   const int Nimg = (int)xp.size(0), Cin = (int)xp.size(3);
   const int H = (int)H64, W = (int)W64;
   const int Hp = H + 2, Wp = W + 2;
-  const int Ho = (H - 1) / (int)stride + 1, Wo = (W - 1) / (int)stride + 1;
+  const int Ho = out_extent(H, stride), Wo = out_extent(W, stride);
   const int M = Nimg * Ho * Wo;
   const int Cout = (int)dy.size(dy_padded ? 3 : 1);
   if (dy_padded) {
@@ -1038,28 +911,16 @@ torch::Tensor gemm_tn3x3_splitk_padded(torch::Tensor dy, torch::Tensor xp,
   auto dyc = dy.contiguous();
   auto s = cur_stream();
   const int nchunks = (M + 63) / 64;
-  if (splitk <= 0) {
-    const int tiles = (Cout / (Cout % 128 == 0 ? 128 : 64)) *
-                      (9 * Cin / (Cin % 128 == 0 ? 128 : 64));
-    splitk = std::max<int64_t>(1, 512 / std::max(1, tiles));
-  }
+  if (splitk <= 0)
+    splitk = auto_splitk(tn_tiles(Cout) * 9 * tn_tiles(Cin), nchunks);
   splitk = std::min<int64_t>(splitk, nchunks);
-  torch::Tensor c;
-  int perm = 0;
-  if (out.has_value()) {
-    // direct-grad mode: accumulate straight into the conv weight's
-    // bucket-view gradient. A 2-D [Cout, 9*Cin] out (channels-last
-    // bucket storage) takes the kernel's NATIVE s-major epilogue —
-    // coalesced; a [Cout, Cin, 3, 3] out takes the perm remap
-    // (stride-9 scatter, kept for the standard layout).
-    c = *out;
-    TORCH_CHECK(c.is_contiguous() && c.scalar_type() == torch::kFloat32 &&
-                    c.numel() == (int64_t)Cout * Cin * 9,
-                "gemm_tn3x3_splitk: out fp32 contiguous");
-    perm = (c.dim() == 2 && c.size(1) == 9 * Cin) ? 0 : Cin;
-  } else {
-    c = torch::zeros({Cout, 9 * Cin}, xp.options().dtype(torch::kFloat32));
-  }
+  auto c = out_or_zeros(out, Cout, 9 * Cin, xp.options(),
+                        "gemm_tn3x3_splitk: out fp32 contiguous");
+  // A 2-D [Cout, 9*Cin] target (channels-last bucket storage, or the fresh
+  // zeros) takes the kernel's NATIVE s-major epilogue — coalesced; a
+  // [Cout, Cin, 3, 3] one takes the perm remap (stride-9 scatter, kept
+  // for the standard layout).
+  const int perm = (c.dim() == 2 && c.size(1) == 9 * Cin) ? 0 : Cin;
   if (dy_padded)
     launch_gemm_tn3x3_splitk_apad(dyc.data_ptr(), xp.data_ptr(),
                                   c.data_ptr<float>(), Cout, Cin, M, Ho, Wo,
@@ -1112,98 +973,71 @@ Conv3x3Geom conv3x3_geom(const torch::Tensor& xp, const torch::Tensor& w3,
   TORCH_CHECK(g.Cin % 64 == 0 && g.Cout % 64 == 0, "conv3x3: C % 64");
   g.Hp = (int)H + 2;
   g.Wp = (int)W + 2;
-  g.Hout = ((int)H + 2 - 3) / (int)stride + 1;
-  g.Wout = ((int)W + 2 - 3) / (int)stride + 1;
+  g.Hout = out_extent(H, stride);
+  g.Wout = out_extent(W, stride);
   g.M = (long long)xp.size(0) * g.Hout * g.Wout;
   return g;
 }
 
-void check_conv3x3_x(const torch::Tensor& x) {
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16,
-              "conv3x3: 4-D bf16 GPU tensor required");
-  TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "conv3x3: channels_last required");
-  TORCH_CHECK(x.size(1) % 64 == 0, "conv3x3: C % 64");
+// xp: zero-halo padded input [N, H+2, W+2, Cin] bf16; w3: [Cout, 9*Cin].
+// Returns {y2d [M, Cout]} or, with_stats, {y2d, BN stats partials of the
+// output [tiles_m, 2*Cout]}. Split-K shapes can't fold stats (sumsq is
+// nonlinear over partial sums) — the second return is then an undefined
+// tensor (Python None).
+std::vector<torch::Tensor> conv3x3_fwd_impl(const torch::Tensor& xp,
+                                            const torch::Tensor& w3,
+                                            int64_t stride, int64_t H,
+                                            int64_t W, bool with_stats) {
+  const Conv3x3Geom g = conv3x3_geom(xp, w3, stride, H, W);
+  const int M = (int)g.M;
+  auto s = cur_stream();
+  const int splitk = conv3x3_pick_splitk(M, g.Cout, g.Cin);
+  torch::Tensor y, bpart;
+  if (splitk > 1) {
+    // CU-starved deep-K shape: fp32 split-K partials + cast
+    // pooled pre-zeroed fold target; cast_bf16_zero returns it clean
+    auto part =
+        part_pool_get(M, g.Cout, xp.options().dtype(torch::kFloat32));
+    launch_conv3x3(xp.data_ptr(), w3.data_ptr(), nullptr, M, g.Cout, g.Cin,
+                   g.Hout * g.Wout, g.Wout, g.Hp, g.Wp, (int)stride,
+                   part.data_ptr<float>(), splitk, nullptr, s);
+    y = torch::empty({g.M, g.Cout}, xp.options());
+    launch_cast_bf16_zero(part.data_ptr<float>(), y.data_ptr(),
+                          g.M * g.Cout, s);
+  } else {
+    y = torch::empty({g.M, g.Cout}, xp.options());
+    if (with_stats)
+      bpart = stats_part_buf(conv3x3_tiles_m(M, g.Cout), 2 * g.Cout,
+                             xp.options());
+    launch_conv3x3(xp.data_ptr(), w3.data_ptr(), y.data_ptr(), M, g.Cout,
+                   g.Cin, g.Hout * g.Wout, g.Wout, g.Hp, g.Wp, (int)stride,
+                   nullptr, 1, with_stats ? bpart.data_ptr<float>() : nullptr,
+                   s);
+  }
+  return {y, bpart};  // bpart undefined without stats
 }
 
 torch::Tensor conv3x3_fwd_padded(torch::Tensor xp, torch::Tensor w3,
                                  int64_t stride, int64_t H, int64_t W) {
-  // xp: zero-halo padded input [N, H+2, W+2, Cin] bf16; w3: [Cout, 9*Cin]
-  const Conv3x3Geom g = conv3x3_geom(xp, w3, stride, H, W);
-  const int Cin = g.Cin, Cout = g.Cout, Hp = g.Hp, Wp = g.Wp;
-  const int Hout = g.Hout, Wout = g.Wout;
-  const long long M = g.M;
-  const torch::Tensor& x = xp;  // options source
-  auto s = cur_stream();
-  const int splitk = conv3x3_pick_splitk((int)M, Cout, Cin);
-  if (splitk > 1) {
-    // CU-starved deep-K shape: fp32 split-K partials + cast
-    // pooled pre-zeroed fold target; cast_bf16_zero returns it clean
-    auto part = part_pool_get((int)M, Cout, x.options().dtype(torch::kFloat32));
-    launch_conv3x3(xp.data_ptr(), w3.data_ptr(), nullptr, (int)M, Cout, Cin,
-                   Hout * Wout, Wout, Hp, Wp, (int)stride,
-                   part.data_ptr<float>(), splitk, nullptr, s);
-    auto y = torch::empty({M, Cout}, x.options());
-    launch_cast_bf16_zero(part.data_ptr<float>(), y.data_ptr(),
-                          (long long)M * Cout, s);
-    return y;
-  }
-  auto y = torch::empty({M, Cout}, x.options());
-  launch_conv3x3(xp.data_ptr(), w3.data_ptr(), y.data_ptr(), (int)M, Cout, Cin,
-                 Hout * Wout, Wout, Hp, Wp, (int)stride, nullptr, 1, nullptr,
-                 s);
-  return y;
-}
-
-torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
-  // x: 4-D channels_last bf16 [N, C, H, W] (pads, then the call above)
-  check_conv3x3_x(x);
-  return conv3x3_fwd_padded(pad_nhwc(x), w3, stride, x.size(2), x.size(3));
+  return conv3x3_fwd_impl(xp, w3, stride, H, W, false)[0];
 }
 
 std::vector<torch::Tensor> conv3x3_fwd_stats_padded(torch::Tensor xp,
                                                     torch::Tensor w3,
                                                     int64_t stride, int64_t H,
                                                     int64_t W) {
-  // conv3x3_fwd_padded + BN stats partials of the output ([tiles_m,
-  // 2*Cout]). Split-K shapes can't fold stats (sumsq is nonlinear over
-  // partial sums) — the second return is then an undefined tensor (Python
-  // None).
-  const Conv3x3Geom g = conv3x3_geom(xp, w3, stride, H, W);
-  const int Cin = g.Cin, Cout = g.Cout, Hp = g.Hp, Wp = g.Wp;
-  const int Hout = g.Hout, Wout = g.Wout;
-  const long long M = g.M;
-  const torch::Tensor& x = xp;  // options source
-  auto s = cur_stream();
-  const int splitk = conv3x3_pick_splitk((int)M, Cout, Cin);
-  if (splitk > 1) {
-    auto part = part_pool_get((int)M, Cout, x.options().dtype(torch::kFloat32));
-    launch_conv3x3(xp.data_ptr(), w3.data_ptr(), nullptr, (int)M, Cout, Cin,
-                   Hout * Wout, Wout, Hp, Wp, (int)stride,
-                   part.data_ptr<float>(), splitk, nullptr, s);
-    auto y = torch::empty({M, Cout}, x.options());
-    launch_cast_bf16_zero(part.data_ptr<float>(), y.data_ptr(),
-                          (long long)M * Cout, s);
-    return {y, torch::Tensor()};
-  }
-  auto y = torch::empty({M, Cout}, x.options());
-  const int tiles_m = conv3x3_tiles_m((int)M, Cout);
-  const int rows = std::min(tiles_m, 192);
-  auto bpart = tiles_m > rows
-                   ? part_pool_get(rows, 2 * Cout,
-                                   x.options().dtype(torch::kFloat32))
-                   : torch::empty({rows, 2 * Cout},
-                                  x.options().dtype(torch::kFloat32));
-  launch_conv3x3(xp.data_ptr(), w3.data_ptr(), y.data_ptr(), (int)M, Cout, Cin,
-                 Hout * Wout, Wout, Hp, Wp, (int)stride, nullptr, 1,
-                 bpart.data_ptr<float>(), s);
-  return {y, bpart};
+  return conv3x3_fwd_impl(xp, w3, stride, H, W, true);
+}
+
+// the unpadded twins: x 4-D channels_last bf16 [N, C, H, W], padded here
+torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
+  check_nhwc_bf16(x, "conv3x3", 64);
+  return conv3x3_fwd_padded(pad_nhwc(x), w3, stride, x.size(2), x.size(3));
 }
 
 std::vector<torch::Tensor> conv3x3_fwd_stats(torch::Tensor x, torch::Tensor w3,
                                              int64_t stride) {
-  check_conv3x3_x(x);
+  check_nhwc_bf16(x, "conv3x3", 64);
   return conv3x3_fwd_stats_padded(pad_nhwc(x), w3, stride, x.size(2),
                                   x.size(3));
 }
@@ -1216,17 +1050,12 @@ torch::Tensor gemm_tn3x3_small(torch::Tensor dy2d, torch::Tensor x,
   // Cout columns first (caller zero-pads); x: 4-D channels_last bf16,
   // Cin <= 64. Returns [64, N2v]; caller slices [:Cout, :9*CinP] and
   // re-lays to [Cout, Cin, 3, 3].
-  TORCH_CHECK(x.is_cuda() && x.dim() == 4 &&
-                  x.scalar_type() == torch::kBFloat16 &&
-                  x.is_contiguous(torch::MemoryFormat::ChannelsLast),
-              "tn3x3s: x 4-D channels_last bf16");
+  check_nhwc_bf16(x, "tn3x3s");
   TORCH_CHECK(stride == 1 || stride == 2, "tn3x3s: stride 1 or 2");
   const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
   const int H = (int)x.size(2), W = (int)x.size(3);
   TORCH_CHECK(Cin >= 1 && Cin <= 64, "tn3x3s: Cin <= 64");
-  const int Hp = H + 2, Wp = W + 2;
-  const int Hout = (H - 1) / (int)stride + 1;
-  const int Wout = (W - 1) / (int)stride + 1;
+  const int Hout = out_extent(H, stride), Wout = out_extent(W, stride);
   const long long M = (long long)Nimg * Hout * Wout;
   TORCH_CHECK(dy2d.is_cuda() && dy2d.is_contiguous() && dy2d.dim() == 2 &&
                   dy2d.scalar_type() == torch::kBFloat16 &&
@@ -1237,22 +1066,14 @@ torch::Tensor gemm_tn3x3_small(torch::Tensor dy2d, torch::Tensor x,
   const int N2 = 9 * CinP;
   const int N2v = (N2 + 63) / 64 * 64;
   auto s = cur_stream();
-  auto xp = torch::empty({(long long)Nimg * Hp * Wp * CinP}, x.options());
-  if (Cin == CinP) {
-    launch_pad_nhwc(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp, Cin, s);
-  } else {
-    launch_pad_nhwc_cpad(x.data_ptr(), xp.data_ptr(), Nimg, H, W, Hp, Wp,
-                         Cin, CinP, s);
-  }
+  auto xp = pad_nhwc_flat(x, CinP, s);
   if (splitk <= 0) {
-    const int tiles = N2v / 64;
-    splitk = std::max<int64_t>(1, 512 / std::max(1, tiles));
     const int nch = (int)((M + 63) / 64);
-    splitk = std::min<int64_t>(splitk, std::max(1, nch));
+    splitk = auto_splitk(N2v / 64, std::max(1, nch));
   }
   auto c = torch::zeros({64, N2v}, x.options().dtype(torch::kFloat32));
   launch_gemm_tn3x3_small(dy2d.data_ptr(), xp.data_ptr(), c.data_ptr<float>(),
-                          64, N2v, (int)M, Hout, Wout, Hp, Wp, CinP,
+                          64, N2v, (int)M, Hout, Wout, H + 2, W + 2, CinP,
                           (int)stride, (int)splitk, s);
   return c;
 }
@@ -1304,12 +1125,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_fwd_eval", &bn_fwd_eval, "fused NHWC bf16 BN(+add)+ReLU eval fwd");
   m.def("bn_bwd", &bn_bwd,
         "fused BN(+add)+ReLU bwd -> (dx, dgamma, dbeta, dres?)",
-        pybind11::arg("dy"), pybind11::arg("msk"), pybind11::arg("x"),
-        pybind11::arg("mean"), pybind11::arg("invstd"), pybind11::arg("gamma"),
-        pybind11::arg("relu"), pybind11::arg("add"), pybind11::arg("training"),
-        pybind11::arg("dgamma_acc") = pybind11::none(),
-        pybind11::arg("dbeta_acc") = pybind11::none(),
-        pybind11::arg("pad_hw") = pybind11::none());
+        py::arg("dy"), py::arg("msk"), py::arg("x"), py::arg("mean"),
+        py::arg("invstd"), py::arg("gamma"), py::arg("relu"), py::arg("add"),
+        py::arg("training"), py::arg("dgamma_acc") = py::none(),
+        py::arg("dbeta_acc") = py::none(), py::arg("pad_hw") = py::none());
   m.def("pad_nhwc", &pad_nhwc,
         "channels_last bf16 [N,C,H,W] -> zero-halo padded [N,H+2,W+2,C]");
   m.def("conv3x3_fwd_padded", &conv3x3_fwd_padded,
@@ -1338,19 +1157,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("transpose_pad", &transpose_pad,
         "bf16 [M,C] -> [C, ceil64(M)] transpose with zero pad");
   m.def("gemm_bt_splitk", &gemm_bt_splitk,
-        "split-K bt GEMM -> fp32 C (wgrad shapes)", pybind11::arg("a"),
-        pybind11::arg("b"), pybind11::arg("splitk") = 0);
+        "split-K bt GEMM -> fp32 C (wgrad shapes)", py::arg("a"), py::arg("b"),
+        py::arg("splitk") = 0);
   m.def("gemm_tn3x3_splitk", &gemm_tn3x3_splitk,
         "direct conv3x3 wgrad: fp32 dW3[Cout,9Cin] = dY^T @ gather3x3(pad(x))",
-        pybind11::arg("dy2d"), pybind11::arg("x"), pybind11::arg("stride"),
-        pybind11::arg("splitk") = 0, pybind11::arg("out") = pybind11::none());
+        py::arg("dy2d"), py::arg("x"), py::arg("stride"), py::arg("splitk") = 0,
+        py::arg("out") = py::none());
   m.def("gemm_tn3x3_small", &gemm_tn3x3_small, py::arg("dy2d"),
         py::arg("x"), py::arg("stride"), py::arg("splitk") = 0,
         "stem wgrad: dY^T @ gather3x3(cpad(x)) -> fp32 [64, N2v] (G3S)");
   m.def("gemm_tn_splitk", &gemm_tn_splitk,
         "split-K TN GEMM: fp32 C[N1,N2] = A[K,N1]^T @ B[K,N2] (direct wgrad)",
-        pybind11::arg("a"), pybind11::arg("b"), pybind11::arg("splitk") = 0,
-        pybind11::arg("out") = pybind11::none());
+        py::arg("a"), py::arg("b"), py::arg("splitk") = 0,
+        py::arg("out") = py::none());
   m.def("conv3x3_wgrad_operand", &conv3x3_wgrad_operand,
         "padded shifted transpose of conv3x3 input -> [9*Cin, Mp]");
   m.def("avgpool2x2_fwd", &avgpool2x2_fwd, "2x2/s2 ceil avg pool (NHWC bf16)");

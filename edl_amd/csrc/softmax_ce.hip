@@ -23,6 +23,7 @@
 // no target term to loss or gradient (the eps/C smoothing term stays)
 // and, for y_a, reports rank = C (never top-k correct).
 #include "common.h"
+#include "launchers.h"
 
 namespace {
 

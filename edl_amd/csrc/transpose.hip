@@ -8,6 +8,7 @@
 // 64x64 bf16 tiles through LDS; 16B vectorized loads and stores; +8-byte
 // row padding in LDS kills write/read bank conflicts.
 #include "common.h"
+#include "launchers.h"
 
 using bf16 = __hip_bfloat16;
 

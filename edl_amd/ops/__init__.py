@@ -1,7 +1,7 @@
 """edl_amd.ops — the CDNA4 HIP kernel layer.
 
 The extension `edl_amd._C` is built IN-TREE for gfx950 only
-(`python setup.py build_ext --inplace`, driven by hipcc with
+(`python build_hip.py`, which drives hipcc directly with
 PYTORCH_ROCM_ARCH=gfx950; see csrc/). There is no CUDA path, no Triton,
 no multi-backend dispatch: on a GPU box the HIP extension is REQUIRED —
 a missing .so raises instead of silently falling back to eager torch
@@ -21,7 +21,7 @@ def _try_load():
     if _EXT is not None or _EXT_ERR is not None:
         return _EXT
     try:
-        from .. import _C  # built in-tree by setup.py build_ext --inplace
+        from .. import _C  # built in-tree by build_hip.py
 
         _EXT = _C
     except ImportError as e:
@@ -40,7 +40,7 @@ def ext():
         if torch.cuda.is_available() and os.environ.get("EDL_ALLOW_NO_EXT") != "1":
             raise RuntimeError(
                 "edl_amd._C HIP extension not built but a GPU is present. "
-                "Build with `python setup.py build_ext --inplace` "
+                "Build with `python build_hip.py` "
                 "(PYTORCH_ROCM_ARCH=gfx950). Original error: %s" % _EXT_ERR
             )
         raise ImportError(str(_EXT_ERR))

@@ -3,16 +3,16 @@
 1x1 convolutions are plain GEMMs: on NHWC input, conv1x1 is
 y[M, Cout] = x[M, Cin] @ W^T — routed through torch.matmul (hipBLASLt on
 ROCm), which runs far closer to the MFMA roofline than MIOpen's igemm
-path at these shapes (igemm measured ~2-4% of bf16 peak at bs32; rocprof
-gpurun_out/prof3). Other shapes stay on F.conv2d (MIOpen) until the
-hand-written implicit-GEMM kernels land.
+path at these shapes (igemm measured ~2-4% of bf16 peak at bs32, by
+rocprof). 3x3 same-pad convolutions run the in-repo implicit-GEMM kernels
+(dense C % 64, small-channel stem, grouped inference); everything else
+stays on F.conv2d (MIOpen).
 
 Weight layout stays nn.Conv2d-compatible ([Cout, Cin, kh, kw]) so state
 dicts interchange."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
-
 
 import os
 
@@ -151,6 +151,16 @@ def bump_weight_epoch():
     _weight_epoch += 1
 
 
+def _out_hw(h, w, stride):
+    """(Ho, Wo) of a 3x3 pad-1 conv."""
+    return (h - 1) // stride + 1, (w - 1) // stride + 1
+
+
+def _nchw_view(y2d, n, h, w):
+    """[N*H*W, C] NHWC-flattened rows -> [N, C, H, W] channels_last view."""
+    return y2d.view(n, h, w, y2d.shape[1]).permute(0, 3, 1, 2)
+
+
 def _repack_w3(weight):
     """[Cout, Cin, 3, 3] -> s-major [Cout, 9*Cin] bf16 contiguous."""
     co, ci = weight.shape[0], weight.shape[1]
@@ -162,8 +172,8 @@ class _Conv3x3Hip(torch.autograd.Function):
     """3x3 same-pad conv on the implicit-GEMM kernel.
 
     dgrad (stride 1) is ANOTHER 3x3 stride-1 conv with rotated/transposed
-    weights on the same kernel; stride-2 dgrad goes through torch.nn.grad
-    (MIOpen); wgrad runs the direct TN gather kernel (Cin<=128) or the
+    weights on the same kernel; stride-2 dgrad is the parity-decomposed
+    kernel; wgrad runs the direct TN gather kernel (Cin<=128) or the
     shift9+split-K pipeline (deeper layers)."""
 
     @staticmethod
@@ -201,18 +211,14 @@ class _Conv3x3Hip(torch.autograd.Function):
             y2d = e.conv3x3_fwd_padded(xp, w3_cached, stride, h, w)
         else:
             y2d = e.conv3x3_fwd(x, w3_cached, stride)
-        ho = (h - 1) // stride + 1
-        wo = (w - 1) // stride + 1
-        co = w_param.shape[0]
-        return y2d.view(n, ho, wo, co).permute(0, 3, 1, 2)
+        return _nchw_view(y2d, n, *_out_hw(h, w, stride))
 
     @staticmethod
     def backward(ctx, dy):
         x, weight = ctx.saved_tensors  # x: padded buffer when ctx.padded
         stride = ctx.stride
         n, cin, h, w = ctx.x_shape
-        ho = (h - 1) // stride + 1
-        wo = (w - 1) // stride + 1
+        ho, wo = _out_hw(h, w, stride)
         # dy straight from the following BN's backward, already in the
         # padded layout? Only if the gradient we were handed IS that
         # buffer's interior — autograd may have summed or copied it.
@@ -223,30 +229,31 @@ class _Conv3x3Hip(torch.autograd.Function):
                 dyp = cand
         if dyp is None:
             dy = dy.contiguous(memory_format=torch.channels_last)
-        if dyp is not None and stride == 1:
-            dx2d = ext().conv3x3_fwd_padded(dyp, ctx.w3rot, 1, ho, wo)
-            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
-        elif dyp is not None:
-            dx2d = ext().conv3x3s2_dgrad_padded(dyp, ctx.w3rot, h, w)
-            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
-        elif stride == 1:
-            dx2d = ext().conv3x3_fwd(dy.to(torch.bfloat16), ctx.w3rot, 1)
-            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
-        elif ctx.w3rot is not None:
-            # stride 2: parity-decomposed implicit-GEMM dgrad (4 class
-            # launches, exact work) — replaces MIOpen's igemm_bwd
-            dx2d = ext().conv3x3s2_dgrad(dy.to(torch.bfloat16), ctx.w3rot, h, w)
-            dx = dx2d.view(n, h, w, cin).permute(0, 3, 1, 2)
-        else:
+        e = ext()
+        if dyp is None and stride == 2 and ctx.w3rot is None:
             dx = torch.nn.grad.conv2d_input(
                 [n, cin, h, w], weight, dy, stride=(stride, stride),
                 padding=(1, 1))
+        else:
+            # stride 1: the forward kernel on rotated weights; stride 2:
+            # parity-decomposed implicit-GEMM dgrad (4 class launches,
+            # exact work) — replaces MIOpen's igemm_bwd. A dy that is not
+            # padded yet goes through the bindings that pad it.
+            if dyp is not None and stride == 1:
+                dx2d = e.conv3x3_fwd_padded(dyp, ctx.w3rot, 1, ho, wo)
+            elif dyp is not None:
+                dx2d = e.conv3x3s2_dgrad_padded(dyp, ctx.w3rot, h, w)
+            elif stride == 1:
+                dx2d = e.conv3x3_fwd(dy.to(torch.bfloat16), ctx.w3rot, 1)
+            else:
+                dx2d = e.conv3x3s2_dgrad(dy.to(torch.bfloat16), ctx.w3rot,
+                                         h, w)
+            dx = _nchw_view(dx2d, n, h, w)
         # wgrad: dW3[Cout, 9Cin] = dY^T @ shift9(x). Default: the direct
         # TN gather kernel reading dY and pad(x) in native NHWC layout
         # (gemm_tn.hip G3 path); fallback "bt": materialize
         # transpose_pad(dy) [Cout, Mp] + shift9_transpose(x) [9Cin, Mp]
         # and run the split-K bt kernel.
-        e = ext()
         co = weight.shape[0]
         ci = weight.shape[1]
         none9 = (None,) * 9
@@ -257,19 +264,15 @@ class _Conv3x3Hip(torch.autograd.Function):
         else:
             dya = dy.permute(0, 2, 3, 1).reshape(-1, co).to(torch.bfloat16)
         if dyp is not None or (_WGRAD == "tn" and ci <= _WGRAD3_MAXC):
+            # grad_tgt: accumulate straight into the bucket-view grad,
+            # laid out [Cout, Cin, 3, 3] (kernel epilogue remaps)
             if ctx.padded:
-                def tn3(*out):
-                    return e.gemm_tn3x3_splitk_padded(dya, x, h, w, stride, 0,
-                                                      *out)
+                dw3 = e.gemm_tn3x3_splitk_padded(dya, x, h, w, stride, 0,
+                                                 ctx.grad_tgt)
             else:
-                def tn3(*out):
-                    return e.gemm_tn3x3_splitk(dya, x, stride, 0, *out)
+                dw3 = e.gemm_tn3x3_splitk(dya, x, stride, 0, ctx.grad_tgt)
             if ctx.grad_tgt is not None:
-                # accumulate straight into the bucket-view grad, laid out
-                # [Cout, Cin, 3, 3] (kernel epilogue remaps)
-                tn3(ctx.grad_tgt)
                 return (dx,) + none9
-            dw3 = tn3()
         else:
             dw3 = e.gemm_bt_splitk(
                 e.transpose_pad(dya),
@@ -326,9 +329,7 @@ class _Conv3x3SmallHip(torch.autograd.Function):
         else:
             y2d = ext().conv3x3_small_fwd(x, w3s, cout, cpt, stride)
         n, _, h, w = x.shape
-        ho = (h - 1) // stride + 1
-        wo = (w - 1) // stride + 1
-        return y2d.view(n, ho, wo, cout).permute(0, 3, 1, 2)
+        return _nchw_view(y2d, n, *_out_hw(h, w, stride))
 
     @staticmethod
     def backward(ctx, dy):
@@ -343,7 +344,7 @@ class _Conv3x3SmallHip(torch.autograd.Function):
             n, _, h, w = x.shape
             cpt = _small_cpt(co)
             dx2d = ext().conv3x3_small_fwd(dyb, ctx.w3srot, ci, cpt, 1)
-            dx = dx2d.view(n, h, w, ci).permute(0, 3, 1, 2)
+            dx = _nchw_view(dx2d, n, h, w)
         # wgrad. Default: torch.nn.grad.conv2d_weight (MIOpen igemm_wrw,
         # ~51 us/call steady). The unfold+hipBLASLt route is kept opt-in
         # (EDL_STEM_WGRAD=unfold) but MEASURED NEGATIVE: hipBLASLt runs
@@ -420,13 +421,14 @@ def _repack_w3_grouped(weight):
 class Conv2dFast(nn.Conv2d):
     """nn.Conv2d drop-in; 1x1/group-1 convs on CUDA bypass MIOpen."""
 
-    def _grad_tgt(self):
+    def _direct_grad(self):
         """Direct-grad mode (reducer sets _edl_direct_grad at world 1):
         the weight's bucket-view gradient, or None. fp32 params only —
-        the wgrad kernels accumulate fp32."""
+        the wgrad kernels accumulate fp32. Each route adds the layout
+        condition its kernel epilogue needs."""
         w = self.weight
         if (getattr(w, "_edl_direct_grad", False) and w.grad is not None
-                and w.grad.dtype == torch.float32 and w.grad.is_contiguous()
+                and w.grad.dtype == torch.float32
                 and torch.is_grad_enabled() and self.training):
             return w.grad
         return None
@@ -474,16 +476,11 @@ class Conv2dFast(nn.Conv2d):
             w3v = mb.permute(0, 2, 3, 1).reshape(co, 9 * ci)
             builders["w3rot"] = lambda: ext().repack_dgrad_w3(w3v, ci, 0)
             builders["w3s2d"] = lambda: ext().repack_dgrad_w3(w3v, ci, 1)
-        if (self.kernel_size == (3, 3) and self.in_channels <= 64
-                and self.out_channels <= 64
-                and (self.in_channels % 64 != 0
-                     or self.out_channels % 64 != 0)):
+        if self._is_small3x3():
             # w3srot only: it is read by BACKWARD (after the engine joins
             # the side stream). w3s is read by FORWARD, which does NOT
             # wait on the prefill stream — prefilling it races.
-            builders["w3srot"] = lambda: _repack_w3_small(
-                self.weight.detach().permute(1, 0, 2, 3).flip(2, 3),
-                _small_cpt(co))
+            builders["w3srot"] = self._build_w3srot
         for k in old_keys:
             b = builders.get(k)
             if b is not None:
@@ -504,15 +501,45 @@ class Conv2dFast(nn.Conv2d):
         self._dy_pad = None
         return p
 
-    def _is_dense3x3(self):
+    def _is_same3x3(self):
+        """What every in-repo 3x3 route needs: 3x3, padding 1, square
+        stride 1 or 2, no bias."""
         return (self.kernel_size == (3, 3)
-                and self.groups == 1
                 and self.padding == (1, 1)
                 and self.stride[0] == self.stride[1]
                 and self.stride[0] in (1, 2)
-                and self.bias is None
+                and self.bias is None)
+
+    def _is_dense3x3(self):
+        return (self._is_same3x3()
+                and self.groups == 1
                 and self.in_channels % 64 == 0
                 and self.out_channels % 64 == 0)
+
+    def _is_small3x3(self):
+        """Deep-stem 3x3s (3->32->32->64): the small-channel kernel."""
+        return (self._is_same3x3()
+                and self.groups == 1
+                and self.in_channels <= 64
+                and self.out_channels <= 64
+                and (self.in_channels % 64 != 0
+                     or self.out_channels % 64 != 0))
+
+    def _is_grouped3x3(self):
+        """Grouped teacher 3x3s. cpg >= _GROUPED_MINC runs the in-repo
+        grouped implicit-GEMM kernel (cpg >= 64: exact, zero wasted MFMA —
+        ResNeXt stage 3/4; cpg 16/32: block-diagonal with 4x/2x zero
+        work). Default MINC=16 routes everything (see _GROUPED_MINC); the
+        r1-measured loss was a cpg=16-ONLY routing, 4x waste with the rest
+        on MIOpen (distill 486 -> 415 img/s). EDL_CONV3X3_GROUPED_MINC to
+        A/B (16 = all, 9999 = none)."""
+        cpg = self.in_channels // self.groups
+        return (self._is_same3x3()
+                and self.groups > 1
+                and self.in_channels == self.out_channels
+                and cpg >= _GROUPED_MINC
+                and cpg in (16, 32, 64, 128)
+                and self.in_channels % 64 == 0)
 
     def takes_padded(self):
         """True if this conv runs the padded-input 3x3 kernels and wants
@@ -520,152 +547,32 @@ class Conv2dFast(nn.Conv2d):
         return (_PAD_ONCE and _BN_PAD_OUT and _CONV3X3 == "hip"
                 and available() and self._is_dense3x3())
 
+    def _build_w3srot(self):
+        # stem dgrad weights: transpose Cin<->Cout + 180° rotate
+        return _repack_w3_small(
+            self.weight.detach().permute(1, 0, 2, 3).flip(2, 3),
+            _small_cpt(self.out_channels))
+
     def forward(self, x, bn_stats=False, dx_pad=False):
         # dx_pad: the caller feeds the output to exactly one BN and will
         # hand it pop_dy_pad()
         self._bn_part = None
         self._dy_pad = None
         bn_stats = bn_stats and _BN_STATS_FUSED
-        if (
-            _CONV3X3 == "hip"
-            and x.is_cuda
-            and available()
-            and x.dtype == torch.bfloat16
-            and self._is_dense3x3()
-        ):
-            # x written by the preceding BN straight into the padded
-            # layout: the buffer rides on the tensor, and is used only if
-            # x still IS its interior view
-            xp = getattr(x, "_edl_xp", None) if _PAD_ONCE else None
-            if not is_interior_of(x, xp):
-                xp = None
-                if not x.is_contiguous(memory_format=torch.channels_last):
-                    x = x.contiguous(memory_format=torch.channels_last)
-            co, ci = self.out_channels, self.in_channels
-            cl = getattr(self.weight, "_edl_phys_shape", None) is not None
-            mb = getattr(self.weight, "_edl_bf16", None)
-            if mb is not None:  # engine bucket mirror: zero-cost bf16 copy
-                w_bf16 = mb
-                wsrc = mb
-            else:
-                w_bf16 = self._cached("w_bf16", lambda: self.weight.detach().to(
-                    torch.bfloat16).contiguous())
-                wsrc = self.weight.detach()
-            if cl and mb is not None:
-                # channels-last bucket: s-major w3 IS the mirror (a view)
-                w3 = mb.permute(0, 2, 3, 1).reshape(co, 9 * ci)
-            else:
-                w3 = self._cached("w3", lambda: _repack_w3(wsrc))
-            if cl and mb is not None:
-                # one-pass kernel repack from the s-major mirror view
-                mode = 0 if self.stride[0] == 1 else 1
-                w3rot = self._cached(
-                    "w3rot" if mode == 0 else "w3s2d",
-                    lambda: ext().repack_dgrad_w3(w3, ci, mode))
-            elif self.stride[0] == 1:
-                w3rot = self._cached("w3rot", lambda: _repack_w3(
-                    wsrc.permute(1, 0, 2, 3).flip(2, 3)))
-            else:
-                w3rot = self._cached("w3s2d",
-                                     lambda: _repack_w3_s2dgrad(wsrc))
-            # direct-grad (world 1): ONLY with channels-last bucket
-            # storage — the wgrad's s-major [Cout, 9Cin] epilogue then IS
-            # the grad-bucket layout (coalesced accumulate). With the
-            # standard layout the stride-9 scatter measured slower than
-            # the AccumulateGrad add it saves (round 1).
-            grad_tgt = None
-            w = self.weight
-            if (cl and getattr(w, "_edl_direct_grad", False)
-                    and w.grad is not None and w.grad.dtype == torch.float32
-                    and ci <= _WGRAD3_MAXC
-                    and torch.is_grad_enabled() and self.training):
-                grad_tgt = w.grad.permute(0, 2, 3, 1).reshape(co, 9 * ci)
-            holder = [] if bn_stats else None
-            # padded dy from the following BN: gather-wgrad layers only
-            # (the deep route's transpose_pad needs a contiguous dy)
-            dyp_holder = None
-            if (dx_pad and _PAD_ONCE and _BN_PAD_DX and _WGRAD == "tn"
-                    and ci <= _WGRAD3_MAXC and w3rot is not None
-                    and torch.is_grad_enabled()):
-                dyp_holder = []
-            y = _Conv3x3Hip.apply(x, self.weight, w_bf16, w3, w3rot,
-                                  self.stride[0], grad_tgt, holder, xp,
-                                  dyp_holder)
-            if holder:
-                self._bn_part = holder[0]
-            self._dy_pad = dyp_holder
-            return y
-        if (
-            # deep-stem 3x3s (3->32->32->64): small-channel kernel
-            _CONV3X3 == "hip"
-            and os.environ.get("EDL_CONV3X3_SMALL", "1") == "1"
-            and x.is_cuda
-            and available()
-            and (x.dtype == torch.bfloat16
-                 or (x.dtype == torch.float32 and torch.is_autocast_enabled()))
-            and self.kernel_size == (3, 3)
-            and self.groups == 1
-            and self.padding == (1, 1)
-            and self.stride[0] == self.stride[1]
-            and self.stride[0] in (1, 2)
-            and self.bias is None
-            and self.in_channels <= 64
-            and self.out_channels <= 64
-            and (self.in_channels % 64 != 0 or self.out_channels % 64 != 0)
-        ):
-            if x.dtype != torch.bfloat16:
-                x = x.to(torch.bfloat16)  # the cast autocast would do
-            if not x.is_contiguous(memory_format=torch.channels_last):
-                x = x.contiguous(memory_format=torch.channels_last)
-            cpt = _small_cpt(self.in_channels)
-            wsrc = self.weight.detach()
-            w3s = self._cached("w3s", lambda: _repack_w3_small(wsrc, cpt))
-            w3srot = None
-            if self.stride[0] == 1 and x.requires_grad:
-                # dgrad weights: transpose Cin<->Cout + 180° rotate
-                w3srot = self._cached("w3srot", lambda: _repack_w3_small(
-                    wsrc.permute(1, 0, 2, 3).flip(2, 3),
-                    _small_cpt(self.out_channels)))
-            holder = [] if bn_stats else None
-            y = _Conv3x3SmallHip.apply(x, self.weight, w3s, w3srot,
-                                       self.stride[0], self.out_channels,
-                                       holder)
-            if holder:
-                self._bn_part = holder[0]
-            return y
-        if (
-            # Grouped teacher 3x3s. cpg >= _GROUPED_MINC runs the in-repo
-            # grouped implicit-GEMM kernel (cpg >= 64: exact, zero wasted
-            # MFMA — ResNeXt stage 3/4; cpg 16/32: block-diagonal with
-            # 4x/2x zero work). Default MINC=32: the r1-measured loss was
-            # the cpg=16-only 4x-waste path (distill 486 -> 415 img/s);
-            # EDL_CONV3X3_GROUPED_MINC to A/B (16 = all, 9999 = none).
-            _CONV3X3 == "hip"
-            and x.is_cuda
-            and available()
-            and x.dtype == torch.bfloat16
-            and self.kernel_size == (3, 3)
-            and self.groups > 1
-            and self.in_channels == self.out_channels
-            and self.in_channels // self.groups >= _GROUPED_MINC
-            and self.in_channels // self.groups in (16, 32, 64, 128)
-            and self.in_channels % 64 == 0
-            and self.padding == (1, 1)
-            and self.stride[0] == self.stride[1]
-            and self.stride[0] in (1, 2)
-            and self.bias is None
-            and not (torch.is_grad_enabled() and
-                     (x.requires_grad or self.weight.requires_grad))
-        ):
-            # grouped teacher convs: eval/inference-only fast path
-            if not x.is_contiguous(memory_format=torch.channels_last):
-                x = x.contiguous(memory_format=torch.channels_last)
-            w3g = self._cached("w3g", lambda: _repack_w3_grouped(self.weight))
-            y2d = ext().conv3x3_grouped_fwd(x, w3g, self.stride[0])
-            n, _, h, w = x.shape
-            ho = (h - 1) // self.stride[0] + 1
-            wo = (w - 1) // self.stride[0] + 1
-            return y2d.view(n, ho, wo, self.out_channels).permute(0, 3, 1, 2)
+        if _CONV3X3 == "hip" and x.is_cuda and available():
+            bf16 = x.dtype == torch.bfloat16
+            if bf16 and self._is_dense3x3():
+                return self._forward_dense3x3(x, bn_stats, dx_pad)
+            if ((bf16 or (x.dtype == torch.float32
+                          and torch.is_autocast_enabled()))
+                    and os.environ.get("EDL_CONV3X3_SMALL", "1") == "1"
+                    and self._is_small3x3()):
+                return self._forward_small3x3(x, bn_stats)
+            if (bf16 and self._is_grouped3x3()
+                    and not (torch.is_grad_enabled() and
+                             (x.requires_grad or self.weight.requires_grad))):
+                # grouped teacher convs: eval/inference-only fast path
+                return self._forward_grouped3x3(x)
         if (
             _CONV1X1 != "miopen"
             and x.is_cuda
@@ -674,44 +581,130 @@ class Conv2dFast(nn.Conv2d):
             and self.padding == (0, 0)
             and self.bias is None
         ):
-            n, c, h, w = x.shape
-            sh, sw = self.stride
-            if sh != 1 or sw != 1:
-                x = x[:, :, ::sh, ::sw].contiguous(memory_format=torch.channels_last)
-                n, c, h, w = x.shape
+            return self._forward_1x1(x, bn_stats)
+        return super().forward(x)
+
+    def _forward_dense3x3(self, x, bn_stats, dx_pad):
+        # x written by the preceding BN straight into the padded layout:
+        # the buffer rides on the tensor, and is used only if x still IS
+        # its interior view
+        xp = getattr(x, "_edl_xp", None) if _PAD_ONCE else None
+        if not is_interior_of(x, xp):
+            xp = None
             if not x.is_contiguous(memory_format=torch.channels_last):
                 x = x.contiguous(memory_format=torch.channels_last)
-            x2d = x.permute(0, 2, 3, 1).reshape(n * h * w, c)
-            wt = self.weight.view(self.out_channels, c)
-            if (
-                _CONV1X1 == "hip"
-                and available()
+        co, ci = self.out_channels, self.in_channels
+        cl = getattr(self.weight, "_edl_phys_shape", None) is not None
+        mb = getattr(self.weight, "_edl_bf16", None)
+        if mb is not None:  # engine bucket mirror: zero-cost bf16 copy
+            w_bf16 = mb
+            wsrc = mb
+        else:
+            w_bf16 = self._cached("w_bf16", lambda: self.weight.detach().to(
+                torch.bfloat16).contiguous())
+            wsrc = self.weight.detach()
+        if cl and mb is not None:
+            # channels-last bucket: s-major w3 IS the mirror (a view)
+            w3 = mb.permute(0, 2, 3, 1).reshape(co, 9 * ci)
+        else:
+            w3 = self._cached("w3", lambda: _repack_w3(wsrc))
+        if cl and mb is not None:
+            # one-pass kernel repack from the s-major mirror view
+            mode = 0 if self.stride[0] == 1 else 1
+            w3rot = self._cached(
+                "w3rot" if mode == 0 else "w3s2d",
+                lambda: ext().repack_dgrad_w3(w3, ci, mode))
+        elif self.stride[0] == 1:
+            w3rot = self._cached("w3rot", lambda: _repack_w3(
+                wsrc.permute(1, 0, 2, 3).flip(2, 3)))
+        else:
+            w3rot = self._cached("w3s2d", lambda: _repack_w3_s2dgrad(wsrc))
+        gather_wgrad = _WGRAD == "tn" and ci <= _WGRAD3_MAXC
+        # direct-grad (world 1): ONLY with channels-last bucket storage —
+        # the wgrad's s-major [Cout, 9Cin] epilogue then IS the grad-bucket
+        # layout (coalesced accumulate). With the standard layout the
+        # stride-9 scatter measured slower than the AccumulateGrad add it
+        # saves (round 1).
+        grad_tgt = None
+        if cl and ci <= _WGRAD3_MAXC:
+            grad_tgt = self._direct_grad()
+            if grad_tgt is not None:
+                grad_tgt = grad_tgt.permute(0, 2, 3, 1).reshape(co, 9 * ci)
+        holder = [] if bn_stats else None
+        # padded dy from the following BN: gather-wgrad layers only (the
+        # deep route's transpose_pad needs a contiguous dy)
+        dyp_holder = None
+        if (dx_pad and _PAD_ONCE and _BN_PAD_DX and gather_wgrad
+                and w3rot is not None and torch.is_grad_enabled()):
+            dyp_holder = []
+        y = _Conv3x3Hip.apply(x, self.weight, w_bf16, w3, w3rot,
+                              self.stride[0], grad_tgt, holder, xp,
+                              dyp_holder)
+        if holder:
+            self._bn_part = holder[0]
+        self._dy_pad = dyp_holder
+        return y
+
+    def _forward_small3x3(self, x, bn_stats):
+        if x.dtype != torch.bfloat16:
+            x = x.to(torch.bfloat16)  # the cast autocast would do
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        cpt = _small_cpt(self.in_channels)
+        w3s = self._cached("w3s", lambda: _repack_w3_small(
+            self.weight.detach(), cpt))
+        w3srot = None
+        if self.stride[0] == 1 and x.requires_grad:
+            w3srot = self._cached("w3srot", self._build_w3srot)
+        holder = [] if bn_stats else None
+        y = _Conv3x3SmallHip.apply(x, self.weight, w3s, w3srot,
+                                   self.stride[0], self.out_channels, holder)
+        if holder:
+            self._bn_part = holder[0]
+        return y
+
+    def _forward_grouped3x3(self, x):
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        w3g = self._cached("w3g", lambda: _repack_w3_grouped(self.weight))
+        y2d = ext().conv3x3_grouped_fwd(x, w3g, self.stride[0])
+        n, _, h, w = x.shape
+        return _nchw_view(y2d, n, *_out_hw(h, w, self.stride[0]))
+
+    def _forward_1x1(self, x, bn_stats):
+        n, c, h, w = x.shape
+        sh, sw = self.stride
+        if sh != 1 or sw != 1:
+            x = x[:, :, ::sh, ::sw].contiguous(memory_format=torch.channels_last)
+            n, c, h, w = x.shape
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        co = self.out_channels
+        x2d = x.permute(0, 2, 3, 1).reshape(n * h * w, c)
+        wt = self.weight.view(co, c)
+        if not (_CONV1X1 == "hip" and available()
                 and x2d.dtype == torch.bfloat16
-                and c % 64 == 0
-                and self.out_channels % 64 == 0
-            ):
-                mb = getattr(self.weight, "_edl_bf16", None)
-                if mb is not None:  # engine bucket mirror: free bf16 view
-                    w_bf16 = mb.view(self.out_channels, c)
-                    # LDS-tiled transpose kernel instead of torch's
-                    # permute-copy (one per 1x1 layer per step);
-                    # transpose_pad is exact here since Cout % 64 == 0
-                    wt_t = self._cached("wt_t", lambda: ext().transpose_pad(
-                        mb.view(self.out_channels, c)))
-                else:
-                    w_bf16 = self._cached("w_bf16", lambda: self.weight.detach()
-                                          .view(self.out_channels, c)
-                                          .to(torch.bfloat16).contiguous())
-                    wt_t = self._cached("wt_t", lambda: self.weight.detach().view(
-                        self.out_channels, c).to(torch.bfloat16).t().contiguous())
-                holder = [] if bn_stats else None
-                y2d = _Conv1x1Hip.apply(x2d, wt, w_bf16, wt_t,
-                                        self._grad_tgt(), holder)
-                if holder:
-                    self._bn_part = holder[0]
-            else:
-                y2d = x2d @ wt.t()
-            return (
-                y2d.view(n, h, w, self.out_channels).permute(0, 3, 1, 2)
-            )
-        return super().forward(x)
+                and c % 64 == 0 and co % 64 == 0):
+            return _nchw_view(x2d @ wt.t(), n, h, w)
+        mb = getattr(self.weight, "_edl_bf16", None)
+        if mb is not None:  # engine bucket mirror: free bf16 view
+            w_bf16 = mb.view(co, c)
+            # LDS-tiled transpose kernel instead of torch's permute-copy
+            # (one per 1x1 layer per step); transpose_pad is exact here
+            # since Cout % 64 == 0
+            wt_t = self._cached("wt_t", lambda: ext().transpose_pad(
+                mb.view(co, c)))
+        else:
+            w_bf16 = self._cached("w_bf16", lambda: self.weight.detach()
+                                  .view(co, c).to(torch.bfloat16).contiguous())
+            wt_t = self._cached("wt_t", lambda: self.weight.detach().view(
+                co, c).to(torch.bfloat16).t().contiguous())
+        # the TN wgrad accumulates into a plain [Cout, Cin] view
+        grad_tgt = self._direct_grad()
+        if grad_tgt is not None and not grad_tgt.is_contiguous():
+            grad_tgt = None
+        holder = [] if bn_stats else None
+        y2d = _Conv1x1Hip.apply(x2d, wt, w_bf16, wt_t, grad_tgt, holder)
+        if holder:
+            self._bn_part = holder[0]
+        return _nchw_view(y2d, n, h, w)
