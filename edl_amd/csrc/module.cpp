@@ -385,6 +385,12 @@ void check_bn_inputs(const torch::Tensor& x, int64_t C) {
   check_bn_inputs_eval(x, C);
   // the training stats/reduce kernels stage 2*C fp32 in LDS
   TORCH_CHECK(C <= 2048, "bn: C <= 2048 supported");
+  // and partition rows by C/8 threads of a 256-thread block (bnrelu.hip
+  // row_partition): exact only when C/8 divides 256
+  TORCH_CHECK((C & (C - 1)) == 0,
+              "bn: training needs a power-of-two C (8..2048): the stats and "
+              "reduce kernels split each 256-thread block into C/8-thread "
+              "rows; got ", C);
 }
 
 std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,

@@ -1,5 +1,7 @@
 """Fused BN(+Add)+ReLU: CPU fallback semantics + GPU kernel numerics vs a
 plain PyTorch fp32 reference of the same op."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -121,6 +123,48 @@ class TestFusedGPU:
             ref = _ref_bn(x, m, relu=True, training=False)
         assert torch.allclose(y.float(), ref, atol=3e-2, rtol=3e-2)
 
+    @pytest.mark.parametrize("C", [24, 40])
+    def test_non_pow2_width_trains_on_fallback(self, C):
+        """C/8 does not divide the 256-thread block: the training kernels'
+        row partition would count some (row, octet) pairs twice or never,
+        so the module must take the torch fallback — output and running
+        stats still match the references."""
+        m, x, _ = self._mk(C)
+        bn = torch.nn.BatchNorm2d(C).cuda()
+        with torch.no_grad():
+            bn.weight.copy_(m.weight)
+            bn.bias.copy_(m.bias)
+        ref = _ref_bn(x.detach(), m, relu=True)  # before m moves its stats
+        rm0, rv0 = m.running_mean.clone(), m.running_var.clone()
+        y = m(x)
+        bn(x.detach().float())
+        assert y.dtype == torch.bfloat16
+        assert torch.allclose(y.float(), ref, atol=3e-2, rtol=3e-2), \
+            (y.float() - ref).abs().max().item()
+        assert torch.allclose(m.running_mean, bn.running_mean, atol=1e-3)
+        assert torch.allclose(m.running_var, bn.running_var, atol=1e-2)
+        assert not torch.allclose(m.running_mean, rm0)
+        assert not torch.allclose(m.running_var, rv0)
+
+    def test_non_pow2_width_kernel_entry_points(self):
+        """The training entry point refuses C = 24; the element-wise eval
+        apply is correct for any C % 8 == 0 and still takes it."""
+        from edl_amd.ops import ext
+
+        C, M = 24, 4 * 9 * 9
+        torch.manual_seed(0)
+        x2d = (torch.randn(M, C, device="cuda") * 2).to(torch.bfloat16)
+        gamma = torch.rand(C, device="cuda") + 0.5
+        beta = torch.randn(C, device="cuda")
+        with pytest.raises(RuntimeError, match="power-of-two"):
+            ext().bn_fwd_train(
+                x2d, gamma, beta, torch.zeros(C, device="cuda"),
+                torch.ones(C, device="cuda"), 0.1, 1e-5, None, True, None)
+        y = ext().bn_fwd_eval(x2d, gamma, beta, None, True)
+        ref = F.relu(x2d.float() * gamma + beta)
+        assert torch.allclose(y.float(), ref, atol=3e-2, rtol=3e-2), \
+            (y.float() - ref).abs().max().item()
+
     def test_resnet50vd_fused_forward_close_to_fallback(self):
         """Whole-model: fused kernels vs the fp32 fallback path."""
         from edl_amd.models import resnet50_vd
@@ -136,6 +180,91 @@ class TestFusedGPU:
             y_ref = model(x)  # fp32, fallback path inside BNReLU2d
         assert torch.allclose(y_fused.float(), y_ref, atol=0.5, rtol=0.1), \
             (y_fused.float() - y_ref).abs().max().item()
+
+
+@functools.lru_cache(maxsize=None)
+def _int_case(M, C, relu, add):
+    """One fwd of the kernels on integer-valued inputs in {1, 2, 3}: exact
+    in bf16, and every per-channel sum stays below 2^24, so fp32 sums are
+    exact in ANY order — a row counted twice or skipped moves them."""
+    from edl_amd.ops import ext
+
+    gen = torch.Generator(device="cuda").manual_seed(50)
+
+    def ints(*shape, dtype):
+        return torch.randint(1, 4, shape, device="cuda",
+                             generator=gen).to(dtype)
+
+    x = ints(M, C, dtype=torch.bfloat16)
+    gamma = ints(C, dtype=torch.float32)
+    beta = ints(C, dtype=torch.float32)
+    res = ints(M, C, dtype=torch.bfloat16) if add else None
+    dy = ints(M, C, dtype=torch.bfloat16)
+    y, mean, invstd, mask = ext().bn_fwd_train(
+        x, gamma, beta, torch.zeros(C, device="cuda"),
+        torch.ones(C, device="cuda"), 0.1, 1e-5, res, relu, None)
+    return dict(x=x, gamma=gamma, dy=dy, mean=mean, invstd=invstd, mask=mask)
+
+
+@pytest.mark.gpu
+class TestReduceLoopsExact:
+    """Both shapes run the 4-stream main loop AND the tail of the stats and
+    backward-reduce row loops: (20736, 64) = grid 192, 6144 rows per grid
+    stride; (196, 2048) = grid 32, 32 rows per grid stride."""
+
+    SHAPES = [(20736, 64), (196, 2048)]
+
+    @pytest.fixture(autouse=True)
+    def _gpu(self):
+        if not torch.cuda.is_available():
+            pytest.skip("no GPU")
+
+    @pytest.mark.parametrize("mc", SHAPES)
+    def test_forward_stats(self, mc):
+        M, C = mc
+        t = _int_case(M, C, True, False)
+        xd = t["x"].double()
+        s = xd.sum(0).float()  # exact integers
+        # the kernel's expression, in fp32: mean = sum * (1 / M)
+        inv_m = (torch.tensor(1.0, dtype=torch.float32) / M).cuda()
+        assert torch.equal(t["mean"], s * inv_m), \
+            (t["mean"] - s * inv_m).abs().max().item()
+        invstd = torch.rsqrt(xd.var(0, unbiased=False) + 1e-5)
+        assert torch.allclose(t["invstd"].double(), invstd, rtol=1e-5, atol=0), \
+            (t["invstd"].double() / invstd - 1).abs().max().item()
+
+    @pytest.mark.parametrize("relu,add", [(True, False), (True, True),
+                                          (False, False)])
+    @pytest.mark.parametrize("mc", SHAPES)
+    def test_backward(self, mc, relu, add):
+        from edl_amd.ops import ext
+
+        M, C = mc
+        t = _int_case(M, C, relu, add)
+        dx, dgamma, dbeta, dres = ext().bn_bwd(
+            t["dy"], t["mask"], t["x"], t["mean"], t["invstd"], t["gamma"],
+            relu, add, True, None, None)
+        # dy_eff from the kernel's own mask: bit k of byte [row, oct] is
+        # channel oct * 8 + k
+        g = t["dy"].double()
+        if relu:
+            bits = (t["mask"].view(M, C // 8, 1).int() >>
+                    torch.arange(8, device="cuda", dtype=torch.int32)) & 1
+            assert 0 < bits.sum().item() < M * C  # both branches of the select
+            g = g * bits.view(M, C)
+        s1 = g.sum(0)
+        assert torch.equal(dbeta, s1.float()), \
+            (dbeta - s1.float()).abs().max().item()
+        invstd = t["invstd"].double()
+        xhat = (t["x"].double() - t["mean"].double()) * invstd
+        s2 = (g * xhat).sum(0)
+        assert torch.allclose(dgamma.double(), s2, atol=2e-1, rtol=2e-2), \
+            (dgamma.double() - s2).abs().max().item()
+        dx_ref = t["gamma"].double() * invstd * (g - s1 / M - xhat * s2 / M)
+        assert torch.allclose(dx.double(), dx_ref, atol=5e-2, rtol=5e-2), \
+            (dx.double() - dx_ref).abs().max().item()
+        if add:
+            assert torch.allclose(dres.double(), g, atol=5e-2, rtol=5e-2)
 
 
 @pytest.mark.gpu

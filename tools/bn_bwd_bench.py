@@ -3,16 +3,13 @@
 
 Measured r1: BN backward = ~2.7 ms/step of a 10.4 ms step; roofline
 (read dy+x+mask twice, write dx once at 6.3 TB/s) is ~0.62 ms. This
-sweeps the ResNet50_vd bs32 BN shapes across:
-  * EDL_BN_BWD_GRID_CAP   (reduce grid: 192 = r1 default / 384 / 768)
-  * EDL_BN_BWD_STREAMS    (4 = r1 / 8 row streams)
-  * EDL_BN_FIN_V2         (strip-parallel finalize vs v1)
-and reports us + achieved GB/s vs roofline per shape.
+sweeps the ResNet50_vd bs32 BN shapes across EDL_BN_BWD_GRID_CAP (reduce
+grid: 192 = default / 384 / 768) and reports us + achieved GB/s vs
+roofline per shape.
 
     python tools/bn_bwd_bench.py [--iters 20]
 """
 import argparse
-import itertools
 import json
 import os
 import sys
@@ -53,13 +50,7 @@ def main():
     e = ops.ext()
     torch.manual_seed(3)
 
-    # (cap, streams, fin_v2, contig)
-    variants = [("192", "4", "0", "0"),  # r1 baseline
-                ("192", "4", "1", "0"),  # r2 shipped default
-                ("192", "4", "1", "1"),  # contiguous block rows
-                ("384", "4", "1", "1"),
-                ("768", "4", "1", "1"),
-                ("192", "8", "1", "1")]
+    caps = ["192", "384", "768"]  # 192 = shipped default
 
     tensors = {}
     for (M, C, relu, add, w) in SHAPES:
@@ -73,13 +64,9 @@ def main():
         tensors[(M, C, relu, add)] = (dy, mask, x, mean, invstd, gamma)
 
     summary = {}
-    for cap, st, fv2, contig in variants:
+    for cap in caps:
         os.environ["EDL_BN_BWD_GRID_CAP"] = cap
-        os.environ["EDL_BN_BWD_STREAMS"] = st
-        os.environ["EDL_BN_FIN_V2"] = fv2
-        os.environ["EDL_BN_CONTIG"] = contig
-        key = "cap%s_st%s_fin%s%s" % (cap, st, "v2" if fv2 == "1" else "v1",
-                                      "_contig" if contig == "1" else "")
+        key = "cap%s" % cap
         total_us = 0.0
         rows = []
         for (M, C, relu, add, w) in SHAPES:
