@@ -23,6 +23,17 @@ void launch_fused_sgd_f32(float* p, const float* g, float* m, float lr,
                           float mu, float wd, float scale, long long n,
                           const float* lr_dev, hipStream_t stream);
 
+// ---- fused_adam.hip ---- (step_dev BEFORE lr_dev; omb = 1-b and ln_b in
+// double on the host; seg tables device pointers, null with nseg == 0)
+constexpr int kAdamMaxSegments = 1024;  // LDS table: 8 B per segment
+void launch_fused_adam_f32(float* p, const float* g, float* m, float* v,
+                           const int* step_dev, const float* lr_dev, float lr,
+                           float b1, float b2, float omb1, float omb2,
+                           float ln_b1, float ln_b2, float eps, float wd,
+                           float scale, int decoupled, long long n,
+                           const int* seg_end, const float* seg_wd, int nseg,
+                           hipStream_t stream);
+
 // ---- kd_loss.hip ----
 void launch_kd_ce_fwd_f32(const float* s, const float* t, float* lpr, int B,
                           int C, hipStream_t stream);

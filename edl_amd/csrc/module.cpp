@@ -1,5 +1,7 @@
 // Python bindings for the edl_amd CDNA4 kernel layer (edl_amd._C).
 // Compiled by hipcc directly (no hipify, no CUDA path) — see build_hip.py.
+#include <iterator>
+#include <mutex>
 #include <unordered_map>
 #include <unordered_set>
 #include <torch/extension.h>
@@ -225,6 +227,133 @@ void fused_sgd(torch::Tensor p, torch::Tensor g, torch::Tensor m, double lr,
   launch_fused_sgd_f32(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                        (float)lr, (float)momentum, (float)weight_decay,
                        (float)grad_scale, (long long)p.numel(), lrp, cur_stream());
+}
+
+// ---- fused Adam / AdamW (fused_adam.hip) ---------------------------------
+
+// The decay table lives on the device, so checking it costs a D2H sync: a
+// table TENSOR is checked on its first eager launch and again whenever its
+// version counter or n changes. The record holds a weak reference to the
+// tensor (which pins the tensor's header, never its storage), so a record
+// cannot pass for a new tensor that lands on the same address. A launch under stream capture cannot
+// sync and skips the check (FusedAdam checks its tables on the host when it
+// builds them); the kernel clamps every table index, so even an unchecked
+// table cannot read out of bounds.
+struct AdamTableSeen {
+  c10::weak_intrusive_ptr<c10::TensorImpl> impl;
+  uint32_t version;
+  long long n;
+};
+
+void adam_check_table(const torch::Tensor& seg_end, long long n) {
+  static std::mutex mu;
+  static std::unordered_map<const c10::TensorImpl*, AdamTableSeen> seen;
+  std::lock_guard<std::mutex> lock(mu);
+  const c10::TensorImpl* key = seg_end.unsafeGetTensorImpl();
+  const uint32_t version = seg_end._version();
+  auto it = seen.find(key);
+  // a live weak reference pins the TensorImpl's address: same key, same
+  // tensor
+  if (it != seen.end() && !it->second.impl.expired() &&
+      it->second.version == version && it->second.n == n)
+    return;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess,
+              "fused_adam: hipStreamIsCapturing failed");
+  if (cap != hipStreamCaptureStatusNone) return;
+  auto host = seg_end.cpu();
+  const int* e = host.data_ptr<int>();
+  int prev = 0;
+  for (int64_t k = 0; k < host.numel(); ++k) {
+    TORCH_CHECK(e[k] >= prev, "fused_adam: seg_end must not decrease");
+    prev = e[k];
+  }
+  TORCH_CHECK(prev == n, "fused_adam: last seg_end (", prev,
+              ") must equal numel (", n, ")");
+  for (auto e = seen.begin(); e != seen.end();)  // drop dead tensors' records
+    e = e->second.impl.expired() ? seen.erase(e) : std::next(e);
+  seen.insert_or_assign(
+      key, AdamTableSeen{c10::weak_intrusive_ptr<c10::TensorImpl>(
+                             seg_end.getIntrusivePtr()),
+                         version, n});
+}
+
+void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                torch::Tensor v, torch::Tensor step_dev, double lr,
+                double beta1, double beta2, double eps, double weight_decay,
+                double grad_scale, bool decoupled,
+                c10::optional<torch::Tensor> lr_dev,
+                c10::optional<torch::Tensor> seg_end,
+                c10::optional<torch::Tensor> seg_wd) {
+  TORCH_CHECK(p.is_cuda() && g.is_cuda() && m.is_cuda() && v.is_cuda(),
+              "fused_adam: GPU tensors required");
+  TORCH_CHECK(p.scalar_type() == torch::kFloat32 &&
+                  g.scalar_type() == torch::kFloat32 &&
+                  m.scalar_type() == torch::kFloat32 &&
+                  v.scalar_type() == torch::kFloat32,
+              "fused_adam: fp32 only");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() &&
+                  v.is_contiguous(),
+              "fused_adam: contiguous flat buffers required");
+  const long long n = p.numel();
+  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n,
+              "fused_adam: size mismatch");
+  TORCH_CHECK(g.device() == p.device() && m.device() == p.device() &&
+                  v.device() == p.device(),
+              "fused_adam: p, g, m, v must share a device");
+  for (const torch::Tensor* t : {&p, &g, &m, &v})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "fused_adam: p, g, m, v must be 16-byte aligned (float4)");
+  TORCH_CHECK(step_dev.is_cuda() && step_dev.device() == p.device() &&
+                  step_dev.scalar_type() == torch::kInt32 &&
+                  step_dev.numel() == 1,
+              "fused_adam: step_dev must be an int32 GPU scalar");
+  TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
+              "fused_adam: betas must lie in [0, 1)");
+  const float* lrp = nullptr;
+  if (lr_dev.has_value()) {
+    TORCH_CHECK(lr_dev->is_cuda() && lr_dev->device() == p.device() &&
+                    lr_dev->scalar_type() == torch::kFloat32 &&
+                    lr_dev->numel() == 1,
+                "fused_adam: lr_dev must be a fp32 GPU scalar");
+    lrp = lr_dev->data_ptr<float>();
+  }
+  const int* endp = nullptr;
+  const float* wdp = nullptr;
+  int nseg = 0;
+  TORCH_CHECK(seg_end.has_value() == seg_wd.has_value(),
+              "fused_adam: seg_end and seg_wd come together");
+  if (seg_end.has_value()) {
+    TORCH_CHECK(seg_end->is_cuda() && seg_wd->is_cuda() &&
+                    seg_end->device() == p.device() &&
+                    seg_wd->device() == p.device() &&
+                    seg_end->scalar_type() == torch::kInt32 &&
+                    seg_wd->scalar_type() == torch::kFloat32 &&
+                    seg_end->is_contiguous() && seg_wd->is_contiguous() &&
+                    seg_end->dim() == 1 && seg_wd->dim() == 1,
+                "fused_adam: seg_end int32 / seg_wd fp32 flat GPU tensors");
+    TORCH_CHECK(seg_end->numel() == seg_wd->numel(),
+                "fused_adam: seg_end and seg_wd differ in length");
+    TORCH_CHECK(seg_end->numel() >= 1 &&
+                    seg_end->numel() <= kAdamMaxSegments,
+                "fused_adam: 1 <= segments <= ", kAdamMaxSegments,
+                " per bucket (got ", seg_end->numel(), ")");
+    TORCH_CHECK(n < (1LL << 31),
+                "fused_adam: a segment table needs numel < 2^31");
+    adam_check_table(*seg_end, n);
+    endp = seg_end->data_ptr<int>();
+    wdp = seg_wd->data_ptr<float>();
+    nseg = (int)seg_end->numel();
+  }
+  if (n == 0) return;
+  // 1-b and ln b in double: the float forms lose ~6e-5 relative on 1-b2
+  launch_fused_adam_f32(
+      p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+      v.data_ptr<float>(), step_dev.data_ptr<int>(), lrp, (float)lr,
+      (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+      (float)std::log(beta1), (float)std::log(beta2), (float)eps,
+      (float)weight_decay, (float)grad_scale, decoupled ? 1 : 0, n, endp, wdp,
+      nseg, cur_stream());
 }
 
 torch::Tensor kd_ce_forward(torch::Tensor s, torch::Tensor t) {
@@ -1092,6 +1221,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("p"), py::arg("g"), py::arg("m"), py::arg("lr"),
         py::arg("momentum"), py::arg("weight_decay"), py::arg("grad_scale"),
         py::arg("lr_dev") = py::none());
+  m.def("fused_adam", &fused_adam,
+        "fused flat Adam/AdamW update (p,g,m,v flat fp32; step count and lr "
+        "read from device scalars; optional per-segment decay table of at "
+        "most 1024 segments); does not advance step_dev",
+        py::arg("p"), py::arg("g"), py::arg("m"), py::arg("v"),
+        py::arg("step_dev"), py::arg("lr"), py::arg("beta1"),
+        py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
+        py::arg("grad_scale"), py::arg("decoupled"),
+        py::arg("lr_dev") = py::none(), py::arg("seg_end") = py::none(),
+        py::arg("seg_wd") = py::none());
+  m.attr("ADAM_MAX_SEGMENTS") = kAdamMaxSegments;
   m.def("dgc_workspace_words", &dgc_workspace_words,
         "int32 words of the (zero-initialised) DGC select workspace");
   m.def("dgc_accumulate", &dgc_accumulate,

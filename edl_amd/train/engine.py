@@ -116,6 +116,10 @@ class TrainerEngine:
         dgc_rampup_step=1,
         fused_ce=False,
         track_accuracy=False,
+        optimizer="momentum",
+        betas=(0.9, 0.999),
+        eps=1e-8,
+        no_decay_1d=False,
     ):
         self.model_name = model
         self.per_device_batch = per_device_batch
@@ -152,6 +156,20 @@ class TrainerEngine:
                 "DGC momentum correction cannot run under the fp16 loss "
                 "scaler: a changing loss scale corrupts the accumulated "
                 "gradients (use bf16 or fp32)")
+        # "momentum" (FusedSGD) | "adam" (L2 decay) | "adamw" (decoupled
+        # decay), the latter two on ops/adam.py with betas / eps;
+        # no_decay_1d exempts biases and BN/LayerNorm scale and shift (the
+        # reference's .*layer_norm_scale|.*layer_norm_bias|.*b_0 pattern)
+        if optimizer not in ("momentum", "adam", "adamw"):
+            raise ValueError("optimizer must be momentum, adam or adamw")
+        if optimizer != "momentum" and dgc:
+            # as the reference: its Adam strategy does not support DGC
+            raise ValueError("DGC needs the momentum optimizer, not %s"
+                             % optimizer)
+        self.optimizer = optimizer
+        self.betas = (float(betas[0]), float(betas[1]))
+        self.eps = float(eps)
+        self.no_decay_1d = bool(no_decay_1d)
         # hard-label loss on the fused softmax-CE kernel (ops.functional.
         # softmax_cross_entropy) instead of F.cross_entropy; mixup labels
         # always take it (torch has no two-label loss)
@@ -270,7 +288,11 @@ class TrainerEngine:
 
         if not (dist.is_initialized() and dist.get_world_size() > 1):
             return
-        if hasattr(self.opt, "_materialize"):
+        if hasattr(self.opt, "state_buffers"):
+            # FusedAdam: m, v and the step counter
+            for t in self.opt.state_buffers():
+                dist.broadcast(t, src=src)
+        elif hasattr(self.opt, "_materialize"):
             for bk in self.opt._materialize():
                 dist.broadcast(bk["m"], src=src)
 
@@ -300,6 +322,16 @@ class TrainerEngine:
             mirror.copy_(flat, non_blocking=True)
 
     def _build_optimizer(self):
+        if self.optimizer != "momentum":
+            from ..ops.adam import FusedAdam
+
+            return FusedAdam(
+                self.model.parameters(), lr=self.base_lr, betas=self.betas,
+                eps=self.eps, weight_decay=self.weight_decay,
+                decoupled=self.optimizer == "adamw",
+                no_decay=(lambda p: p.ndim <= 1) if self.no_decay_1d else None,
+                grad_scale=self.reducer.grad_scale, reducer=self.reducer,
+            )
         from ..ops.sgd import FusedSGD
 
         return FusedSGD(
@@ -319,7 +351,11 @@ class TrainerEngine:
     def scaled_lr(self, epoch, step_in_epoch=0.0):
         """Linear-scaling rule: base_lr is quoted at total batch 256
         (reference train_parameters, models/resnet_vd.py) and rescales on
-        every elastic world change."""
+        every elastic world change. adam / adamw: base_lr as it is — the
+        reference's adam strategy is a constant LR with no linear scaling
+        and no piecewise decay (train_with_fleet.py:196-200)."""
+        if self.optimizer != "momentum":
+            return self.base_lr
         lr = self.base_lr * self.global_batch / 256.0
         return piecewise_lr(lr, epoch, step_in_epoch=step_in_epoch)
 
@@ -453,8 +489,11 @@ class TrainerEngine:
                      for b in self.reducer._buckets])
                 found_inf = not bool(flags.all().item())
                 if not self.scaler.update(found_inf):
+                    # overflow: skip the update, scale backed off. opt.step()
+                    # never runs, so FusedAdam's step count t (and with it
+                    # the bias corrections) does not advance either.
                     self.global_step += 1
-                    return loss  # overflow: skip the update, scale backed off
+                    return loss
                 inv_scale = 1.0 / self.scaler.value
             if getattr(self.opt, "handles_grad_scale", False):
                 if inv_scale != 1.0:

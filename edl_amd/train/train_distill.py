@@ -48,6 +48,16 @@ def parse_args(argv=None):
                    help="CxHxW of the synthetic student input (e.g. "
                         "1x28x28 for the mnist_* students)")
     p.add_argument("--num_classes", type=int, default=1000)
+    # reference example/distill/nlp/model.py:35-51: AdamW students with
+    # biases and norm scales excluded from decay
+    p.add_argument("--optimizer", default="momentum",
+                   choices=["momentum", "adam", "adamw"])
+    p.add_argument("--beta1", type=float, default=0.9)
+    p.add_argument("--beta2", type=float, default=0.999)
+    p.add_argument("--epsilon", type=float, default=1e-8)
+    p.add_argument("--no_decay_1d", type=int, default=0,
+                   help="adam/adamw: no weight decay on biases and norm "
+                        "scale/shift (params with ndim <= 1)")
     return p.parse_args(argv)
 
 
@@ -64,6 +74,10 @@ def main(argv=None):
         use_hip_ops=torch.cuda.is_available(),
         kd_alpha=args.kd_alpha,
         num_classes=args.num_classes,
+        optimizer=args.optimizer,
+        betas=(args.beta1, args.beta2),
+        eps=args.epsilon,
+        no_decay_1d=bool(args.no_decay_1d),
     ).setup(tenv)
     engine.model.train()
 

@@ -70,6 +70,16 @@ def parse_args(argv=None):
                    help="steps over which --dgc_sparsity is walked")
     p.add_argument("--dgc_sparsity", default="0.999",
                    help="comma list, e.g. 0.75,0.9375,0.984375,0.996,0.999")
+    # reference train_with_fleet.py:196-200 `adam` strategy (constant LR);
+    # adamw = decoupled decay
+    p.add_argument("--optimizer", default="momentum",
+                   choices=["momentum", "adam", "adamw"])
+    p.add_argument("--beta1", type=float, default=0.9)
+    p.add_argument("--beta2", type=float, default=0.999)
+    p.add_argument("--epsilon", type=float, default=1e-8)
+    p.add_argument("--no_decay_1d", type=int, default=0,
+                   help="adam/adamw: no weight decay on biases and BN "
+                        "scale/shift (params with ndim <= 1)")
     return p.parse_args(argv)
 
 
@@ -97,6 +107,10 @@ def main(argv=None):
         dgc_rampup=args.rampup_begin_step,
         dgc_rampup_step=args.rampup_step,
         dgc_sparsity=[float(x) for x in args.dgc_sparsity.split(",") if x],
+        optimizer=args.optimizer,
+        betas=(args.beta1, args.beta2),
+        eps=args.epsilon,
+        no_decay_1d=bool(args.no_decay_1d),
     ).setup(tenv)
 
     # status reporting back to the control plane (reference TrainStatus flow,

@@ -33,6 +33,10 @@ def main(argv=None):
     p.add_argument("--steps_per_epoch", type=int, default=100)
     p.add_argument("--lr", type=float, default=0.01)
     p.add_argument("--checkpoint", default=None)
+    # the reference trains ctr and fit_a_line with Adam
+    # (example/ctr/ctr/train.py:234)
+    p.add_argument("--optimizer", default="momentum",
+                   choices=["momentum", "adam"])
     p.add_argument("--data_dir", default=None,
                    help="fit_a_line only: directory of text files "
                         "('f1 ... f13 y' per line) read through the ELASTIC "
@@ -51,9 +55,15 @@ def main(argv=None):
         data = SyntheticCTR(args.batch_size, device,
                             seed=1234 + tenv.global_rank)
     reducer = BucketedAllReducer(model.parameters(), bucket_cap_mb=4)
-    opt = FusedSGD(model.parameters(), lr=args.lr, momentum=0.9,
-                   weight_decay=0.0, grad_scale=reducer.grad_scale,
-                   reducer=reducer)
+    if args.optimizer == "adam":
+        from ..ops.adam import FusedAdam
+
+        opt = FusedAdam(model.parameters(), lr=args.lr,
+                        grad_scale=reducer.grad_scale, reducer=reducer)
+    else:
+        opt = FusedSGD(model.parameters(), lr=args.lr, momentum=0.9,
+                       weight_decay=0.0, grad_scale=reducer.grad_scale,
+                       reducer=reducer)
     ckpt = CheckpointManager(args.checkpoint) if args.checkpoint else None
     start_epoch = 0
     if ckpt:
