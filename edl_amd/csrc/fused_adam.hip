@@ -86,7 +86,11 @@ extern "C" __global__ void fused_adam_f32(
     const float b2, const float omb1, const float omb2, const float ln_b1,
     const float ln_b2, const float eps, const float wd, const float scale,
     const int decoupled, const long long n, const int* __restrict__ seg_end,
-    const float* __restrict__ seg_wd, const int nseg) {
+    const float* __restrict__ seg_wd, const int nseg,
+    const float* __restrict__ clip) {
+  // clip = [coef, norm, skip, nskipped] of grad_norm.hip, or null: a skipped
+  // step leaves before any store or barrier (uniform)
+  if (clip && clip[2] != 0.0f) return;
   extern __shared__ int s_tab[];  // [nseg] ends, then [nseg] decays
   int* s_end = s_tab;
   float* s_wd = reinterpret_cast<float*>(s_tab + nseg);
@@ -104,7 +108,9 @@ extern "C" __global__ void fused_adam_f32(
   const int t = *step_dev;
   const float tf = (float)(t > 1 ? t : 1);
   c.b1 = b1; c.b2 = b2; c.omb1 = omb1; c.omb2 = omb2;
-  c.eps = eps; c.scale = scale; c.decoupled = decoupled != 0;
+  // coef == 1.0f is bitwise the null path
+  c.eps = eps; c.scale = clip ? scale * clip[0] : scale;
+  c.decoupled = decoupled != 0;
   c.step_size = c.lr / -expm1f(tf * ln_b1);
   c.sqrt_bc2 = sqrtf(-expm1f(tf * ln_b2));
 
@@ -157,12 +163,12 @@ extern "C" void launch_fused_adam_f32(
     const float* lr_dev, float lr, float b1, float b2, float omb1, float omb2,
     float ln_b1, float ln_b2, float eps, float wd, float scale, int decoupled,
     long long n, const int* seg_end, const float* seg_wd, int nseg,
-    hipStream_t stream) {
+    const float* clip, hipStream_t stream) {
   const int block = 256;
   const int grid = elementwise_grid((n + 3) / 4, block);
   const size_t lds = (size_t)nseg * (sizeof(int) + sizeof(float));
   hipLaunchKernelGGL(fused_adam_f32, dim3(grid), dim3(block), lds, stream, p,
                      g, m, v, step_dev, lr_dev, lr, b1, b2, omb1, omb2, ln_b1,
                      ln_b2, eps, wd, scale, decoupled, n, seg_end, seg_wd,
-                     nseg);
+                     nseg, clip);
 }

@@ -13,8 +13,17 @@
 
 extern "C" __global__ void fused_sgd_f32(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-    const float lr_host, const float mu, const float wd, const float scale,
-    const long long n, const float* __restrict__ lr_dev) {
+    const float lr_host, const float mu, const float wd, const float scale_in,
+    const long long n, const float* __restrict__ lr_dev,
+    const float* __restrict__ clip) {
+  // clip = [coef, norm, skip, nskipped] of grad_norm.hip, or null: a skipped
+  // step leaves before any store (uniform), otherwise the clip coefficient
+  // folds into the gradient scale (coef == 1.0f is bitwise the null path)
+  float scale = scale_in;
+  if (clip) {
+    if (clip[2] != 0.0f) return;
+    scale *= clip[0];
+  }
   // lr comes from a device scalar when provided so a hipGraph-captured
   // step picks up LR-schedule changes on replay (the host scalar would be
   // frozen at capture time); one broadcast load, L2-resident.
@@ -55,9 +64,9 @@ extern "C" __global__ void fused_sgd_f32(
 extern "C" void launch_fused_sgd_f32(float* p, const float* g, float* m,
                                      float lr, float mu, float wd, float scale,
                                      long long n, const float* lr_dev,
-                                     hipStream_t stream) {
+                                     const float* clip, hipStream_t stream) {
   const int block = 256;
   const int grid = elementwise_grid((n + 3) / 4, block);
   hipLaunchKernelGGL(fused_sgd_f32, dim3(grid), dim3(block), 0, stream,
-                     p, g, m, lr, mu, wd, scale, n, lr_dev);
+                     p, g, m, lr, mu, wd, scale, n, lr_dev, clip);
 }

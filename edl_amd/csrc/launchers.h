@@ -19,9 +19,11 @@ constexpr int kStatsPartRowCap = 192;
 extern "C" {
 
 // ---- fused_sgd.hip ----
+// (clip: the fp32[4] state grad_clip_finalize writes, or null)
 void launch_fused_sgd_f32(float* p, const float* g, float* m, float lr,
                           float mu, float wd, float scale, long long n,
-                          const float* lr_dev, hipStream_t stream);
+                          const float* lr_dev, const float* clip,
+                          hipStream_t stream);
 
 // ---- fused_adam.hip ---- (step_dev BEFORE lr_dev; omb = 1-b and ln_b in
 // double on the host; seg tables device pointers, null with nseg == 0)
@@ -32,7 +34,34 @@ void launch_fused_adam_f32(float* p, const float* g, float* m, float* v,
                            float ln_b1, float ln_b2, float eps, float wd,
                            float scale, int decoupled, long long n,
                            const int* seg_end, const float* seg_wd, int nseg,
+                           const float* clip, hipStream_t stream);
+
+// ---- grad_norm.hip ---- (sum of squares of up to kGradNormMaxSegs flat
+// fp32 buffers per launch into double partial rows, then one block that
+// turns the rows into state = [coef, norm, skip, nskipped])
+constexpr int kGradNormMaxSegs = 16;
+// Rows (blocks of 256 threads) one buffer gets at most; grad_norm_rows(n)
+// is the count for n elements (>= 1: an empty buffer writes one 0.0 row).
+// Measured on MI355X (tools/clip_bench.py, docs/kernels.md): the reduction
+// runs within 5% of its best anywhere from 256 to 8192 rows in total, best
+// at 512 for one buffer, while the finalize block pays ~1 us per 4096 rows;
+// 512 keeps a single bucket at its best and 16 buckets at 8192 rows.
+constexpr int kGradNormRowCap = 512;
+constexpr int kGradClipStateLen = 4;
+struct GradNormSegs {  // passed to the kernel by value
+  const float* ptr[kGradNormMaxSegs];
+  long long n[kGradNormMaxSegs];
+  int row_off[kGradNormMaxSegs];  // first partial row of the buffer
+  int rows[kGradNormMaxSegs];     // == grad_norm_rows(n)
+  int nseg;
+};
+int grad_norm_rows(long long n);
+void launch_grad_sumsq_f32(const GradNormSegs* segs, double* partial,
                            hipStream_t stream);
+void launch_grad_clip_finalize(const double* partial, int rows_total,
+                               double grad_scale, float max_norm,
+                               int skip_nonfinite, float* state,
+                               hipStream_t stream);
 
 // ---- kd_loss.hip ----
 void launch_kd_ce_fwd_f32(const float* s, const float* t, float* lpr, int B,

@@ -207,9 +207,24 @@ void dgc_scatter_add(torch::Tensor out, torch::Tensor payload) {
                          cur_stream());
 }
 
+// optional fp32[4] clip state [coef, norm, skip, nskipped] on `like`'s
+// device (grad_norm.hip writes it, the update kernels read it) -> pointer
+// or null
+float* clip_state_ptr(const c10::optional<torch::Tensor>& st,
+                      const torch::Tensor& like, const char* who) {
+  if (!st.has_value()) return nullptr;
+  TORCH_CHECK(st->is_cuda() && st->device() == like.device() &&
+                  st->scalar_type() == torch::kFloat32 &&
+                  st->is_contiguous() && st->numel() == kGradClipStateLen,
+              who, ": clip_state must be a contiguous fp32[",
+              kGradClipStateLen, "] tensor on the buffers' device");
+  return st->data_ptr<float>();
+}
+
 void fused_sgd(torch::Tensor p, torch::Tensor g, torch::Tensor m, double lr,
                double momentum, double weight_decay, double grad_scale,
-               c10::optional<torch::Tensor> lr_dev) {
+               c10::optional<torch::Tensor> lr_dev,
+               c10::optional<torch::Tensor> clip_state) {
   TORCH_CHECK(p.is_cuda() && g.is_cuda() && m.is_cuda(), "fused_sgd: GPU tensors required");
   TORCH_CHECK(p.scalar_type() == torch::kFloat32 && g.scalar_type() == torch::kFloat32 &&
                   m.scalar_type() == torch::kFloat32,
@@ -226,7 +241,9 @@ void fused_sgd(torch::Tensor p, torch::Tensor g, torch::Tensor m, double lr,
   }
   launch_fused_sgd_f32(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                        (float)lr, (float)momentum, (float)weight_decay,
-                       (float)grad_scale, (long long)p.numel(), lrp, cur_stream());
+                       (float)grad_scale, (long long)p.numel(), lrp,
+                       clip_state_ptr(clip_state, p, "fused_sgd"),
+                       cur_stream());
 }
 
 // ---- fused Adam / AdamW (fused_adam.hip) ---------------------------------
@@ -284,7 +301,8 @@ void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                 double grad_scale, bool decoupled,
                 c10::optional<torch::Tensor> lr_dev,
                 c10::optional<torch::Tensor> seg_end,
-                c10::optional<torch::Tensor> seg_wd) {
+                c10::optional<torch::Tensor> seg_wd,
+                c10::optional<torch::Tensor> clip_state) {
   TORCH_CHECK(p.is_cuda() && g.is_cuda() && m.is_cuda() && v.is_cuda(),
               "fused_adam: GPU tensors required");
   TORCH_CHECK(p.scalar_type() == torch::kFloat32 &&
@@ -345,6 +363,7 @@ void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
     wdp = seg_wd->data_ptr<float>();
     nseg = (int)seg_end->numel();
   }
+  const float* clipp = clip_state_ptr(clip_state, p, "fused_adam");
   if (n == 0) return;
   // 1-b and ln b in double: the float forms lose ~6e-5 relative on 1-b2
   launch_fused_adam_f32(
@@ -353,7 +372,80 @@ void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
       (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
       (float)std::log(beta1), (float)std::log(beta2), (float)eps,
       (float)weight_decay, (float)grad_scale, decoupled ? 1 : 0, n, endp, wdp,
-      nseg, cur_stream());
+      nseg, clipp, cur_stream());
+}
+
+// ---- global gradient norm / clip state (grad_norm.hip) --------------------
+
+// -> partial rows of the buffers, in order (what grad_sumsq writes)
+int64_t grad_norm_rows_total(const std::vector<torch::Tensor>& bufs) {
+  int64_t total = 0;
+  for (const auto& b : bufs) total += grad_norm_rows((long long)b.numel());
+  return total;
+}
+
+// partial[row] = sum of squares (double) of a slice of one buffer; every row
+// of [0, rows_total) is written. More than kGradNormMaxSegs buffers take
+// further launches of the same kernel. -> rows_total
+int64_t grad_sumsq(std::vector<torch::Tensor> bufs, torch::Tensor partial) {
+  const int64_t rows_total = grad_norm_rows_total(bufs);
+  TORCH_CHECK(partial.is_cuda() && partial.scalar_type() == torch::kFloat64 &&
+                  partial.is_contiguous() && partial.numel() >= rows_total,
+              "grad_sumsq: partial must be a contiguous fp64 GPU tensor of "
+              "at least ", rows_total, " rows (grad_norm_rows per buffer)");
+  for (const auto& b : bufs) {
+    TORCH_CHECK(b.is_cuda(), "grad_sumsq: GPU tensors required");
+    TORCH_CHECK(b.scalar_type() == torch::kFloat32, "grad_sumsq: fp32 only");
+    TORCH_CHECK(b.is_contiguous(),
+                "grad_sumsq: contiguous flat buffers required");
+    TORCH_CHECK(b.device() == partial.device(),
+                "grad_sumsq: buffers and partial must share a device");
+    TORCH_CHECK(b.numel() >= 0, "grad_sumsq: n >= 0");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(b.data_ptr()) % 16 == 0,
+                "grad_sumsq: buffers must be 16-byte aligned (float4)");
+  }
+  auto s = cur_stream();
+  int row = 0;
+  for (size_t base = 0; base < bufs.size(); base += kGradNormMaxSegs) {
+    GradNormSegs segs = {};
+    const size_t cnt = std::min<size_t>(kGradNormMaxSegs, bufs.size() - base);
+    segs.nseg = (int)cnt;
+    for (size_t k = 0; k < cnt; ++k) {
+      const auto& b = bufs[base + k];
+      segs.ptr[k] = b.numel() ? b.data_ptr<float>() : nullptr;
+      segs.n[k] = (long long)b.numel();
+      segs.rows[k] = grad_norm_rows(segs.n[k]);
+      segs.row_off[k] = row;
+      row += segs.rows[k];
+    }
+    launch_grad_sumsq_f32(&segs, partial.data_ptr<double>(), s);
+  }
+  return rows_total;
+}
+
+// state = [coef, norm, skip, nskipped] from partial[0 .. rows_total)
+void grad_clip_finalize(torch::Tensor partial, int64_t rows_total,
+                        torch::Tensor state, double grad_scale,
+                        double max_norm, bool skip_nonfinite) {
+  TORCH_CHECK(partial.is_cuda() && partial.scalar_type() == torch::kFloat64 &&
+                  partial.is_contiguous(),
+              "grad_clip_finalize: partial must be a contiguous fp64 GPU "
+              "tensor");
+  TORCH_CHECK(rows_total >= 0 && rows_total <= partial.numel() &&
+                  rows_total < (1LL << 31),
+              "grad_clip_finalize: 0 <= rows_total <= partial.numel()");
+  TORCH_CHECK(state.is_cuda() && state.device() == partial.device() &&
+                  state.scalar_type() == torch::kFloat32 &&
+                  state.is_contiguous() &&
+                  state.numel() == kGradClipStateLen,
+              "grad_clip_finalize: state must be a contiguous fp32[",
+              kGradClipStateLen, "] tensor on partial's device");
+  TORCH_CHECK(max_norm >= 0.0, "grad_clip_finalize: max_norm >= 0 (inf = "
+                               "norm only)");
+  launch_grad_clip_finalize(partial.data_ptr<double>(), (int)rows_total,
+                            grad_scale, (float)max_norm,
+                            skip_nonfinite ? 1 : 0, state.data_ptr<float>(),
+                            cur_stream());
 }
 
 torch::Tensor kd_ce_forward(torch::Tensor s, torch::Tensor t) {
@@ -1220,7 +1312,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused flat momentum-SGD update (p,g,m flat fp32; folds grad_scale)",
         py::arg("p"), py::arg("g"), py::arg("m"), py::arg("lr"),
         py::arg("momentum"), py::arg("weight_decay"), py::arg("grad_scale"),
-        py::arg("lr_dev") = py::none());
+        py::arg("lr_dev") = py::none(), py::arg("clip_state") = py::none());
+  m.def("grad_norm_rows", [](int64_t n) { return grad_norm_rows(n); },
+        "partial rows grad_sumsq writes for a buffer of n elements",
+        py::arg("n"));
+  m.def("grad_sumsq", &grad_sumsq,
+        "per-block double sums of squares of flat fp32 buffers into "
+        "partial (every row written; 16 buffers per launch) -> rows_total",
+        py::arg("buffers"), py::arg("partial"));
+  m.def("grad_clip_finalize", &grad_clip_finalize,
+        "partial rows -> state [coef, norm, skip, nskipped]: norm = "
+        "grad_scale*sqrt(sum), coef = min(1, max_norm/(norm+1e-6))",
+        py::arg("partial"), py::arg("rows_total"), py::arg("state"),
+        py::arg("grad_scale"), py::arg("max_norm"),
+        py::arg("skip_nonfinite") = false);
+  m.attr("GRAD_NORM_MAX_SEGS") = kGradNormMaxSegs;
+  m.attr("GRAD_NORM_ROW_CAP") = kGradNormRowCap;
   m.def("fused_adam", &fused_adam,
         "fused flat Adam/AdamW update (p,g,m,v flat fp32; step count and lr "
         "read from device scalars; optional per-segment decay table of at "
@@ -1230,7 +1337,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("beta2"), py::arg("eps"), py::arg("weight_decay"),
         py::arg("grad_scale"), py::arg("decoupled"),
         py::arg("lr_dev") = py::none(), py::arg("seg_end") = py::none(),
-        py::arg("seg_wd") = py::none());
+        py::arg("seg_wd") = py::none(), py::arg("clip_state") = py::none());
   m.attr("ADAM_MAX_SEGMENTS") = kAdamMaxSegments;
   m.def("dgc_workspace_words", &dgc_workspace_words,
         "int32 words of the (zero-initialised) DGC select workspace");

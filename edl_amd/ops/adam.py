@@ -163,7 +163,10 @@ class FusedAdam:
         return out
 
     @torch.no_grad()
-    def step(self):
+    def step(self, clip_state=None):
+        """clip_state: the [coef, norm, skip, nskipped] tensor of
+        ops/clip.py GradClipper.run() — the gradient scale is multiplied
+        by coef; skip != 0 leaves p, m, v AND the step count untouched."""
         from .conv import bump_weight_epoch
 
         bump_weight_epoch()  # invalidate per-step weight-derived caches
@@ -174,18 +177,24 @@ class FusedAdam:
         lr, (b1, b2), eps = g0["lr"], g0["betas"], g0["eps"]
         decoupled = g0["decoupled"]
         # once per step for all buckets; an in-place device op, so a graph
-        # capture records it and every replay counts
-        self._step_t.add_(1)
+        # capture records it and every replay counts. With a clip state the
+        # counter advances by 1 - skip, still on the device.
+        if clip_state is None:
+            self._step_t.add_(1)
+        else:
+            self._step_t.add_((1.0 - clip_state[2:3]).to(torch.int32))
         if buckets[0]["p"].is_cuda:
             fused_adam = ext().fused_adam  # a missing kernel is an error
             for bk in buckets:
                 fused_adam(bk["p"], bk["g"], bk["m"], bk["v"], self._step_t,
                            lr, b1, b2, eps, bk["wd"], self.grad_scale,
                            decoupled, self._lr_dev, bk["seg_end"],
-                           bk["seg_wd"])
+                           bk["seg_wd"], clip_state)
             return
         # CPU (tests / bring-up): torch.optim.Adam's own op sequence, with
         # the host step count authoritative
+        if clip_state is not None and bool(clip_state[2] != 0):
+            return  # skipped step
         t = int(self._step_t.item())
         bc1 = 1 - b1 ** t
         bc2 = 1 - b2 ** t
@@ -194,7 +203,10 @@ class FusedAdam:
         for bk in buckets:
             p, m, v = bk["p"], bk["m"], bk["v"]
             g = bk["g"]
-            if self.grad_scale != 1.0:
+            if clip_state is not None:
+                # fp32 product first, as the kernel forms it
+                g = g.mul(clip_state[0] * self.grad_scale)
+            elif self.grad_scale != 1.0:
                 g = g.mul(self.grad_scale)
             start = 0
             for end, wd in bk["segs"]:

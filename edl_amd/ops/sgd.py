@@ -76,11 +76,14 @@ class FusedSGD:
         return out
 
     @torch.no_grad()
-    def step(self, momentum=None, weight_decay=None):
+    def step(self, momentum=None, weight_decay=None, clip_state=None):
         """momentum / weight_decay override the group's values for this
         step only (None = the group's). DGC momentum correction steps
         with 0.0, 0.0: both already live in its accumulators, and with
-        momentum 0 the momentum buffer just mirrors the update."""
+        momentum 0 the momentum buffer just mirrors the update.
+        clip_state: the [coef, norm, skip, nskipped] tensor of
+        ops/clip.py GradClipper.run() — the gradient scale is multiplied
+        by coef, and skip != 0 leaves p and m untouched."""
         from .conv import bump_weight_epoch
 
         bump_weight_epoch()  # invalidate per-step weight-derived caches
@@ -93,11 +96,16 @@ class FusedSGD:
         for bk in self._materialize():
             if self._use_ext and bk["p"].is_cuda:
                 ext().fused_sgd(bk["p"], bk["g"], bk["m"], lr, mu, wd,
-                                self.grad_scale, self._lr_dev)
+                                self.grad_scale, self._lr_dev, clip_state)
             else:
                 # torch fallback (CPU tests / bring-up): same math
                 g = bk["g"]
-                if self.grad_scale != 1.0:
+                if clip_state is not None:
+                    if bool(clip_state[2] != 0):
+                        return  # skipped step: p, m untouched
+                    # fp32 product first, as the kernel forms it
+                    g = g.mul(clip_state[0] * self.grad_scale)
+                elif self.grad_scale != 1.0:
                     g = g.mul(self.grad_scale)
                 g = g.add(bk["p"], alpha=wd)
                 bk["m"].mul_(mu).add_(g)

@@ -120,6 +120,8 @@ class TrainerEngine:
         betas=(0.9, 0.999),
         eps=1e-8,
         no_decay_1d=False,
+        clip_grad_norm=None,
+        skip_nonfinite=False,
     ):
         self.model_name = model
         self.per_device_batch = per_device_batch
@@ -170,6 +172,28 @@ class TrainerEngine:
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = float(eps)
         self.no_decay_1d = bool(no_decay_1d)
+        # clip_grad_norm: clip the global gradient norm (after the DP
+        # average and the fp16 unscale) to this value, as
+        # torch.nn.utils.clip_grad_norm_ would; skip_nonfinite: leave the
+        # parameters and the optimizer state untouched on a step whose norm
+        # is inf/nan. Either one engages ops/clip.py GradClipper (alone,
+        # skip_nonfinite runs it norm-only); all of it stays on the device,
+        # so the step remains capturable.
+        if clip_grad_norm is not None and not float(clip_grad_norm) >= 0.0:
+            raise ValueError("clip_grad_norm must be >= 0")
+        if (clip_grad_norm is not None or skip_nonfinite) and dgc:
+            # both DGC modes: their buckets do not hold the dense gradient
+            # when the optimizer steps
+            raise ValueError("gradient clipping / skip_nonfinite cannot "
+                             "run under DGC")
+        self.clip_grad_norm = (None if clip_grad_norm is None
+                               else float(clip_grad_norm))
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.clipper = None
+        # device tensors ([1] fp32), overwritten each step; None without a
+        # clipper
+        self.last_grad_norm = None
+        self.skipped_steps = None
         # hard-label loss on the fused softmax-CE kernel (ops.functional.
         # softmax_cross_entropy) instead of F.cross_entropy; mixup labels
         # always take it (torch has no two-label loss)
@@ -239,6 +263,11 @@ class TrainerEngine:
             self.dgc = DGCCompressor(self.reducer, self.dgc_cfg[1],
                                      self.dgc_cfg[2])
         self.opt = self._build_optimizer()
+        if self.clip_grad_norm is not None or self.skip_nonfinite:
+            from ..ops.clip import GradClipper
+
+            self.clipper = GradClipper(self.reducer, self.clip_grad_norm,
+                                       self.skip_nonfinite)
         if self.dgc_cfg[0] and self.dgc_momentum_correction:
             from .dgc import DGCMomentum
 
@@ -495,6 +524,14 @@ class TrainerEngine:
                     self.global_step += 1
                     return loss
                 inv_scale = 1.0 / self.scaler.value
+            if self.clipper is not None:
+                # every rank holds the same all-reduced buckets and the
+                # reduction is deterministic: same bits everywhere, no
+                # collective. Two launches, nothing on the host.
+                opt_kw["clip_state"] = self.clipper.run(
+                    self.opt.grad_scale * inv_scale)
+                self.last_grad_norm = self.clipper.norm
+                self.skipped_steps = self.clipper.skipped
             if getattr(self.opt, "handles_grad_scale", False):
                 if inv_scale != 1.0:
                     base = self.opt.grad_scale

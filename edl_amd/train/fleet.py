@@ -37,6 +37,9 @@ class DistributedStrategy:
     # Non-empty (with use_dgc) = DGC with momentum correction.
     dgc_configs: dict = field(default_factory=dict)
     use_recompute: bool = False
+    # global-norm gradient clipping (Paddle: GradientClipByGlobalNorm);
+    # None = off. Refused together with use_dgc.
+    clip_grad_norm: float = None
     extra: dict = field(default_factory=dict)
 
 
@@ -94,6 +97,7 @@ def distributed_engine(model_name="resnet50_vd", strategy=None, **kwargs):
         kwargs.setdefault("dgc_rampup_step", cfg.get("rampup_step", 1))
         kwargs.setdefault("dgc_sparsity", cfg.get("sparsity", [0.999]))
     kwargs.setdefault("recompute", strategy.use_recompute)
+    kwargs.setdefault("clip_grad_norm", strategy.clip_grad_norm)
     eng = TrainerEngine(model=model_name, **kwargs)
     eng.setup(_state["env"])
     return eng

@@ -80,6 +80,12 @@ def parse_args(argv=None):
     p.add_argument("--no_decay_1d", type=int, default=0,
                    help="adam/adamw: no weight decay on biases and BN "
                         "scale/shift (params with ndim <= 1)")
+    p.add_argument("--clip_grad_norm", type=float, default=None,
+                   help="clip the global gradient norm to this value "
+                        "(device-side, capture-safe; not with --use_dgc)")
+    p.add_argument("--skip_nonfinite", type=int, default=0,
+                   help="skip the update of a step whose gradient norm is "
+                        "inf/nan")
     return p.parse_args(argv)
 
 
@@ -111,6 +117,8 @@ def main(argv=None):
         betas=(args.beta1, args.beta2),
         eps=args.epsilon,
         no_decay_1d=bool(args.no_decay_1d),
+        clip_grad_norm=args.clip_grad_norm,
+        skip_nonfinite=bool(args.skip_nonfinite),
     ).setup(tenv)
 
     # status reporting back to the control plane (reference TrainStatus flow,

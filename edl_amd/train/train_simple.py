@@ -37,6 +37,11 @@ def main(argv=None):
     # (example/ctr/ctr/train.py:234)
     p.add_argument("--optimizer", default="momentum",
                    choices=["momentum", "adam"])
+    p.add_argument("--clip_grad_norm", type=float, default=None,
+                   help="clip the global gradient norm to this value")
+    p.add_argument("--skip_nonfinite", type=int, default=0,
+                   help="skip the update of a step whose gradient norm is "
+                        "inf/nan")
     p.add_argument("--data_dir", default=None,
                    help="fit_a_line only: directory of text files "
                         "('f1 ... f13 y' per line) read through the ELASTIC "
@@ -64,6 +69,19 @@ def main(argv=None):
         opt = FusedSGD(model.parameters(), lr=args.lr, momentum=0.9,
                        weight_decay=0.0, grad_scale=reducer.grad_scale,
                        reducer=reducer)
+    clipper = None
+    if args.clip_grad_norm is not None or args.skip_nonfinite:
+        from ..ops.clip import GradClipper
+
+        clipper = GradClipper(reducer, args.clip_grad_norm,
+                              bool(args.skip_nonfinite))
+
+    def opt_step():
+        if clipper is None:
+            opt.step()
+        else:
+            opt.step(clip_state=clipper.run(opt.grad_scale))
+
     ckpt = CheckpointManager(args.checkpoint) if args.checkpoint else None
     start_epoch = 0
     if ckpt:
@@ -145,7 +163,7 @@ def main(argv=None):
                     loss = F.mse_loss(model(x), y)
                     loss.backward()
                 reducer.finalize()
-                opt.step()
+                opt_step()
             log.info("rank %d consumed %d records this epoch",
                      tenv.global_rank, n_recs)
             if ckpt and tenv.is_rank0:
@@ -163,7 +181,7 @@ def main(argv=None):
                     model(dense, sparse), label)
             loss.backward()
             reducer.finalize()
-            opt.step()
+            opt_step()
         if ckpt and tenv.is_rank0:
             ckpt.save(model.state_dict(), {"epoch_no": epoch}, blocking=True)
         if tenv.is_rank0:
