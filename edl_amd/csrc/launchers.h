@@ -63,6 +63,47 @@ void launch_grad_clip_finalize(const double* partial, int rows_total,
                                int skip_nonfinite, float* state,
                                hipStream_t stream);
 
+// ---- fused_lars.hip ---- (per-tensor sums of squares of p and g over up to
+// kLarsMaxBufs buckets per launch, one block per row of the device chunk
+// table; one launch that turns them into trust[tensor]; then the update,
+// one launch per bucket)
+constexpr int kLarsMaxBufs = 16;
+// Elements one block of lars_sumsq_f32 reduces: a chunk never crosses a
+// tensor boundary, so a tensor of n elements owns ceil(n / kLarsChunk)
+// chunks. 8 float4 per lane and array; the largest ResNet50_vd tensor
+// (2.36M elements) owns 288 chunks, which one wave of lars_trust_f32 sums.
+constexpr int kLarsChunk = 8192;
+constexpr int kLarsChunkFields = 4;  // int32 {bucket, start, len, 0} per chunk
+// Chunk partials one wave of lars_trust_f32 loads before it starts adding;
+// a tensor with more chunks takes another pass of the same loop.
+constexpr int kLarsTrustPreload = 512;
+struct LarsBufs {  // passed to the kernel by value
+  const float* p[kLarsMaxBufs];
+  const float* g[kLarsMaxBufs];
+  long long n[kLarsMaxBufs];
+  int first;  // bucket index of slot 0 (the chunk table counts all buckets)
+  int nbuf;
+};
+// partial: double [2 * chunks] = {sum p^2, sum g^2} per chunk; the launch
+// writes chunks [chunk_base, chunk_base + nchunks)
+void launch_lars_sumsq_f32(const LarsBufs* bufs, const int* chunks,
+                           int chunk_base, int nchunks, double* partial,
+                           hipStream_t stream);
+// tensor_chunks: int32 {first chunk, chunk count} per tensor
+void launch_lars_trust_f32(const double* partial, const int* tensor_chunks,
+                           int ntensors, int nchunks_total, double coeff,
+                           double wd, double eps, float grad_scale,
+                           const float* clip, float* trust,
+                           hipStream_t stream);
+// segment tables as fused_adam's (at most kAdamMaxSegments), plus
+// seg_tensor: the slot of `trust` a segment reads
+void launch_fused_lars_f32(float* p, const float* g, float* v,
+                           const float* lr_dev, float lr, float mu,
+                           float scale, long long n, const int* seg_end,
+                           const float* seg_wd, const int* seg_tensor,
+                           int nseg, const float* trust, int ntensors,
+                           const float* clip, hipStream_t stream);
+
 // ---- kd_loss.hip ----
 void launch_kd_ce_fwd_f32(const float* s, const float* t, float* lpr, int B,
                           int C, hipStream_t stream);

@@ -448,6 +448,248 @@ void grad_clip_finalize(torch::Tensor partial, int64_t rows_total,
                             cur_stream());
 }
 
+// ---- fused LARS (fused_lars.hip) ------------------------------------------
+
+// A device table is checked with a D2H copy on its first eager launch and
+// again whenever its version counter or `key` changes (the scheme of
+// adam_check_table, weak reference included). Under stream capture the copy
+// is impossible and the check is skipped: FusedLARS checks the host lists it
+// builds the tables from, and the kernels clamp every table value.
+template <typename F>
+void lars_check_table(const torch::Tensor& table, long long key,
+                      const char* who, F check) {
+  static std::mutex mu;
+  static std::unordered_map<const c10::TensorImpl*, AdamTableSeen> seen;
+  std::lock_guard<std::mutex> lock(mu);
+  const c10::TensorImpl* id = table.unsafeGetTensorImpl();
+  const uint32_t version = table._version();
+  auto it = seen.find(id);
+  if (it != seen.end() && !it->second.impl.expired() &&
+      it->second.version == version && it->second.n == key)
+    return;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess, who,
+              ": hipStreamIsCapturing failed");
+  if (cap != hipStreamCaptureStatusNone) return;
+  auto host = table.cpu();
+  check(host.data_ptr<int>(), host.numel());
+  for (auto e = seen.begin(); e != seen.end();)  // drop dead tensors' records
+    e = e->second.impl.expired() ? seen.erase(e) : std::next(e);
+  seen.insert_or_assign(
+      id, AdamTableSeen{c10::weak_intrusive_ptr<c10::TensorImpl>(
+                            table.getIntrusivePtr()),
+                        version, key});
+}
+
+void lars_check_int_table(const torch::Tensor& t, const torch::Tensor& like,
+                          const char* who, const char* what) {
+  TORCH_CHECK(t.is_cuda() && t.device() == like.device() &&
+                  t.scalar_type() == torch::kInt32 && t.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              who, ": ", what,
+              " must be a contiguous, 16-byte aligned int32 tensor on the "
+              "buffers' device");
+}
+
+// partial[2c], partial[2c+1] = sums of squares (double) of p and g over
+// chunk c of `chunks` (int32 [nchunks, 4] = {bucket, start, len, 0}, sorted
+// by bucket; bucket_chunk_off[b] = first chunk of bucket b, one more entry
+// than buckets). Every chunk's pair is written. More than kLarsMaxBufs
+// buckets take further launches of the same kernel. -> nchunks
+int64_t lars_sumsq(std::vector<torch::Tensor> ps, std::vector<torch::Tensor> gs,
+                   torch::Tensor chunks,
+                   std::vector<int64_t> bucket_chunk_off,
+                   torch::Tensor partial) {
+  const size_t nb = ps.size();
+  TORCH_CHECK(gs.size() == nb && bucket_chunk_off.size() == nb + 1,
+              "lars_sumsq: one g and one chunk offset per p, plus the end");
+  TORCH_CHECK(partial.is_cuda() && partial.scalar_type() == torch::kFloat64 &&
+                  partial.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(partial.data_ptr()) % 16 == 0,
+              "lars_sumsq: partial must be a contiguous, 16-byte aligned "
+              "fp64 GPU tensor");
+  lars_check_int_table(chunks, partial, "lars_sumsq", "chunks");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == kLarsChunkFields,
+              "lars_sumsq: chunks must be int32 [nchunks, ",
+              kLarsChunkFields, "]");
+  const int64_t nchunks = chunks.size(0);
+  TORCH_CHECK(nchunks < (1LL << 30) && partial.numel() >= 2 * nchunks,
+              "lars_sumsq: partial needs 2 slots per chunk (", 2 * nchunks,
+              ")");
+  TORCH_CHECK(bucket_chunk_off[0] == 0 && bucket_chunk_off[nb] == nchunks,
+              "lars_sumsq: bucket_chunk_off must run from 0 to nchunks");
+  long long total = 0;
+  for (size_t b = 0; b < nb; ++b) {
+    TORCH_CHECK(bucket_chunk_off[b] <= bucket_chunk_off[b + 1],
+                "lars_sumsq: bucket_chunk_off must not decrease");
+    for (const torch::Tensor* t : {&ps[b], &gs[b]}) {
+      TORCH_CHECK(t->is_cuda() && t->device() == partial.device(),
+                  "lars_sumsq: buffers and partial must share a GPU");
+      TORCH_CHECK(t->scalar_type() == torch::kFloat32, "lars_sumsq: fp32 only");
+      TORCH_CHECK(t->is_contiguous(),
+                  "lars_sumsq: contiguous flat buffers required");
+      TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                  "lars_sumsq: buffers must be 16-byte aligned (float4)");
+    }
+    TORCH_CHECK(ps[b].numel() == gs[b].numel() &&
+                    ps[b].numel() < (1LL << 31),
+                "lars_sumsq: p and g of a bucket must agree, numel < 2^31");
+    total += (long long)ps[b].numel();
+  }
+  lars_check_table(chunks, total, "lars_sumsq", [&](const int* e, int64_t) {
+    int prev = 0;
+    for (int64_t c = 0; c < nchunks; ++c, e += kLarsChunkFields) {
+      TORCH_CHECK(e[0] >= prev && e[0] < (int64_t)nb &&
+                      c >= bucket_chunk_off[e[0]] &&
+                      c < bucket_chunk_off[e[0] + 1],
+                  "lars_sumsq: chunk ", c, " names bucket ", e[0],
+                  " outside its bucket_chunk_off range");
+      prev = e[0];
+      TORCH_CHECK(e[1] >= 0 && e[2] >= 0 && e[2] <= kLarsChunk &&
+                      (int64_t)e[1] + e[2] <= ps[e[0]].numel(),
+                  "lars_sumsq: chunk ", c, " [", e[1], ", +", e[2],
+                  ") leaves its bucket or exceeds ", kLarsChunk, " elements");
+    }
+  });
+  auto s = cur_stream();
+  for (size_t base = 0; base < nb; base += kLarsMaxBufs) {
+    LarsBufs bufs = {};
+    const size_t cnt = std::min<size_t>(kLarsMaxBufs, nb - base);
+    bufs.first = (int)base;
+    bufs.nbuf = (int)cnt;
+    for (size_t k = 0; k < cnt; ++k) {
+      const auto& p = ps[base + k];
+      bufs.p[k] = p.numel() ? p.data_ptr<float>() : nullptr;
+      bufs.g[k] = p.numel() ? gs[base + k].data_ptr<float>() : nullptr;
+      bufs.n[k] = (long long)p.numel();
+    }
+    const int64_t lo = bucket_chunk_off[base], hi = bucket_chunk_off[base + cnt];
+    launch_lars_sumsq_f32(&bufs, chunks.data_ptr<int>(), (int)lo,
+                          (int)(hi - lo), partial.data_ptr<double>(), s);
+  }
+  return nchunks;
+}
+
+// trust[k] = coeff*pn/(gn + wd*pn + eps) from the chunk partials of tensor k
+// (tensor_chunks: int32 [ntensors, 2] = {first chunk, count}); 1.0 for a
+// tensor without chunks or with pn, gn or wd not > 0. Every slot is written.
+void lars_trust(torch::Tensor partial, int64_t nchunks,
+                torch::Tensor tensor_chunks, torch::Tensor trust,
+                double lars_coeff, double lars_weight_decay, double epsilon,
+                double grad_scale, c10::optional<torch::Tensor> clip_state) {
+  TORCH_CHECK(partial.is_cuda() && partial.scalar_type() == torch::kFloat64 &&
+                  partial.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(partial.data_ptr()) % 16 == 0,
+              "lars_trust: partial must be a contiguous, 16-byte aligned "
+              "fp64 GPU tensor");
+  TORCH_CHECK(nchunks >= 0 && nchunks < (1LL << 30) &&
+                  2 * nchunks <= partial.numel(),
+              "lars_trust: 0 <= 2 * nchunks <= partial.numel()");
+  lars_check_int_table(tensor_chunks, partial, "lars_trust", "tensor_chunks");
+  TORCH_CHECK(tensor_chunks.dim() == 2 && tensor_chunks.size(1) == 2 &&
+                  tensor_chunks.size(0) >= 1 &&
+                  tensor_chunks.size(0) < (1LL << 30),
+              "lars_trust: tensor_chunks must be int32 [ntensors >= 1, 2]");
+  const int64_t nt = tensor_chunks.size(0);
+  TORCH_CHECK(trust.is_cuda() && trust.device() == partial.device() &&
+                  trust.scalar_type() == torch::kFloat32 &&
+                  trust.is_contiguous() && trust.numel() >= nt,
+              "lars_trust: trust must be a contiguous fp32 tensor of at "
+              "least ntensors slots on partial's device");
+  TORCH_CHECK(lars_coeff >= 0.0 && lars_weight_decay >= 0.0 && epsilon >= 0.0,
+              "lars_trust: lars_coeff, lars_weight_decay, epsilon >= 0");
+  lars_check_table(tensor_chunks, nchunks, "lars_trust",
+                   [&](const int* e, int64_t) {
+    for (int64_t k = 0; k < nt; ++k, e += 2)
+      TORCH_CHECK(e[0] >= 0 && e[1] >= 0 && (int64_t)e[0] + e[1] <= nchunks,
+                  "lars_trust: tensor ", k, " owns chunks [", e[0], ", +",
+                  e[1], ") of ", nchunks);
+  });
+  launch_lars_trust_f32(partial.data_ptr<double>(),
+                        tensor_chunks.data_ptr<int>(), (int)nt, (int)nchunks,
+                        lars_coeff, lars_weight_decay, epsilon,
+                        (float)grad_scale,
+                        clip_state_ptr(clip_state, partial, "lars_trust"),
+                        trust.data_ptr<float>(), cur_stream());
+}
+
+void fused_lars(torch::Tensor p, torch::Tensor g, torch::Tensor v, double lr,
+                double momentum, double grad_scale, torch::Tensor seg_end,
+                torch::Tensor seg_wd, torch::Tensor seg_tensor,
+                torch::Tensor trust, c10::optional<torch::Tensor> lr_dev,
+                c10::optional<torch::Tensor> clip_state) {
+  TORCH_CHECK(p.is_cuda() && g.is_cuda() && v.is_cuda(),
+              "fused_lars: GPU tensors required");
+  TORCH_CHECK(p.scalar_type() == torch::kFloat32 &&
+                  g.scalar_type() == torch::kFloat32 &&
+                  v.scalar_type() == torch::kFloat32,
+              "fused_lars: fp32 only");
+  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && v.is_contiguous(),
+              "fused_lars: contiguous flat buffers required");
+  const long long n = p.numel();
+  TORCH_CHECK(g.numel() == n && v.numel() == n, "fused_lars: size mismatch");
+  TORCH_CHECK(g.device() == p.device() && v.device() == p.device(),
+              "fused_lars: p, g, v must share a device");
+  for (const torch::Tensor* t : {&p, &g, &v})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "fused_lars: p, g, v must be 16-byte aligned (float4)");
+  TORCH_CHECK(n < (1LL << 31), "fused_lars: the segment table needs numel < "
+                               "2^31");
+  const float* lrp = nullptr;
+  if (lr_dev.has_value()) {
+    TORCH_CHECK(lr_dev->is_cuda() && lr_dev->device() == p.device() &&
+                    lr_dev->scalar_type() == torch::kFloat32 &&
+                    lr_dev->numel() == 1,
+                "fused_lars: lr_dev must be a fp32 GPU scalar");
+    lrp = lr_dev->data_ptr<float>();
+  }
+  lars_check_int_table(seg_end, p, "fused_lars", "seg_end");
+  lars_check_int_table(seg_tensor, p, "fused_lars", "seg_tensor");
+  TORCH_CHECK(seg_wd.is_cuda() && seg_wd.device() == p.device() &&
+                  seg_wd.scalar_type() == torch::kFloat32 &&
+                  seg_wd.is_contiguous(),
+              "fused_lars: seg_wd must be a contiguous fp32 tensor on the "
+              "buffers' device");
+  const int64_t nseg = seg_end.numel();
+  TORCH_CHECK(seg_end.dim() == 1 && seg_wd.dim() == 1 &&
+                  seg_tensor.dim() == 1 && seg_wd.numel() == nseg &&
+                  seg_tensor.numel() == nseg,
+              "fused_lars: seg_end, seg_wd, seg_tensor differ in length");
+  TORCH_CHECK(nseg >= 1 && nseg <= kAdamMaxSegments,
+              "fused_lars: 1 <= segments <= ", kAdamMaxSegments,
+              " per bucket (got ", nseg, ")");
+  TORCH_CHECK(trust.is_cuda() && trust.device() == p.device() &&
+                  trust.scalar_type() == torch::kFloat32 &&
+                  trust.is_contiguous() && trust.numel() >= 1 &&
+                  trust.numel() < (1LL << 31),
+              "fused_lars: trust must be a non-empty contiguous fp32 tensor "
+              "on the buffers' device");
+  lars_check_table(seg_end, n, "fused_lars", [&](const int* e, int64_t cnt) {
+    int prev = 0;
+    for (int64_t k = 0; k < cnt; ++k) {
+      TORCH_CHECK(e[k] >= prev, "fused_lars: seg_end must not decrease");
+      prev = e[k];
+    }
+    TORCH_CHECK(prev == n, "fused_lars: last seg_end (", prev,
+                ") must equal numel (", n, ")");
+  });
+  lars_check_table(seg_tensor, trust.numel(), "fused_lars",
+                   [&](const int* e, int64_t cnt) {
+    for (int64_t k = 0; k < cnt; ++k)
+      TORCH_CHECK(e[k] >= 0 && e[k] < trust.numel(),
+                  "fused_lars: seg_tensor[", k, "] = ", e[k],
+                  " is no slot of trust (", trust.numel(), ")");
+  });
+  const float* clipp = clip_state_ptr(clip_state, p, "fused_lars");
+  if (n == 0) return;
+  launch_fused_lars_f32(p.data_ptr<float>(), g.data_ptr<float>(),
+                        v.data_ptr<float>(), lrp, (float)lr, (float)momentum,
+                        (float)grad_scale, n, seg_end.data_ptr<int>(),
+                        seg_wd.data_ptr<float>(), seg_tensor.data_ptr<int>(),
+                        (int)nseg, trust.data_ptr<float>(),
+                        (int)trust.numel(), clipp, cur_stream());
+}
+
 torch::Tensor kd_ce_forward(torch::Tensor s, torch::Tensor t) {
   TORCH_CHECK(s.is_cuda() && t.is_cuda(), "kd_ce: GPU tensors required");
   TORCH_CHECK(s.dim() == 2 && t.sizes() == s.sizes(), "kd_ce: [B,C] logits expected");
@@ -1339,6 +1581,32 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lr_dev") = py::none(), py::arg("seg_end") = py::none(),
         py::arg("seg_wd") = py::none(), py::arg("clip_state") = py::none());
   m.attr("ADAM_MAX_SEGMENTS") = kAdamMaxSegments;
+  m.def("lars_sumsq", &lars_sumsq,
+        "LARS: double sums of squares of p and g per row of the chunk table "
+        "(int32 [nchunks, 4] = {bucket, start, len, 0}) into partial "
+        "[2 * nchunks]; every pair written; 16 buckets per launch "
+        "-> nchunks",
+        py::arg("ps"), py::arg("gs"), py::arg("chunks"),
+        py::arg("bucket_chunk_off"), py::arg("partial"));
+  m.def("lars_trust", &lars_trust,
+        "LARS: chunk partials -> trust[k] = coeff*pn/(gn + wd*pn + eps) per "
+        "tensor (1.0 without chunks or with pn, gn or wd not > 0), "
+        "gn = grad_scale * clip coef * sqrt(sum g^2)",
+        py::arg("partial"), py::arg("nchunks"), py::arg("tensor_chunks"),
+        py::arg("trust"), py::arg("lars_coeff"),
+        py::arg("lars_weight_decay"), py::arg("epsilon"),
+        py::arg("grad_scale"), py::arg("clip_state") = py::none());
+  m.def("fused_lars", &fused_lars,
+        "fused flat LARS momentum update (p,g,v flat fp32): v = mu*v + "
+        "lr*trust[seg_tensor]*(scale*g + seg_wd*p); p -= v; at most 1024 "
+        "segments; lr read from the device scalar when given",
+        py::arg("p"), py::arg("g"), py::arg("v"), py::arg("lr"),
+        py::arg("momentum"), py::arg("grad_scale"), py::arg("seg_end"),
+        py::arg("seg_wd"), py::arg("seg_tensor"), py::arg("trust"),
+        py::arg("lr_dev") = py::none(), py::arg("clip_state") = py::none());
+  m.attr("LARS_CHUNK") = kLarsChunk;
+  m.attr("LARS_MAX_BUFS") = kLarsMaxBufs;
+  m.attr("LARS_TRUST_PRELOAD") = kLarsTrustPreload;
   m.def("dgc_workspace_words", &dgc_workspace_words,
         "int32 words of the (zero-initialised) DGC select workspace");
   m.def("dgc_accumulate", &dgc_accumulate,

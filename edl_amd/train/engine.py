@@ -122,6 +122,9 @@ class TrainerEngine:
         no_decay_1d=False,
         clip_grad_norm=None,
         skip_nonfinite=False,
+        lars_coeff=0.001,
+        lars_eps=0.0,
+        lars_exclude=None,
     ):
         self.model_name = model
         self.per_device_batch = per_device_batch
@@ -162,8 +165,12 @@ class TrainerEngine:
         # decay), the latter two on ops/adam.py with betas / eps;
         # no_decay_1d exempts biases and BN/LayerNorm scale and shift (the
         # reference's .*layer_norm_scale|.*layer_norm_bias|.*b_0 pattern)
-        if optimizer not in ("momentum", "adam", "adamw"):
-            raise ValueError("optimizer must be momentum, adam or adamw")
+        # "lars" (ops/lars.py FusedLARS): momentum with a per-tensor trust
+        # ratio; weight_decay is the LARS decay, lars_coeff / lars_eps its
+        # coefficient and epsilon, no_decay_1d (or lars_exclude, a list of
+        # parameter-name substrings) excludes tensors from it
+        if optimizer not in ("momentum", "adam", "adamw", "lars"):
+            raise ValueError("optimizer must be momentum, adam, adamw or lars")
         if optimizer != "momentum" and dgc:
             # as the reference: its Adam strategy does not support DGC
             raise ValueError("DGC needs the momentum optimizer, not %s"
@@ -172,6 +179,12 @@ class TrainerEngine:
         self.betas = (float(betas[0]), float(betas[1]))
         self.eps = float(eps)
         self.no_decay_1d = bool(no_decay_1d)
+        self.lars_coeff = float(lars_coeff)
+        self.lars_eps = float(lars_eps)
+        self.lars_exclude = tuple(lars_exclude or ())
+        # device tensor (fp32, one entry per parameter), overwritten each
+        # step; None unless optimizer == "lars"
+        self.last_trust_ratios = None
         # clip_grad_norm: clip the global gradient norm (after the DP
         # average and the fp16 unscale) to this value, as
         # torch.nn.utils.clip_grad_norm_ would; skip_nonfinite: leave the
@@ -318,7 +331,7 @@ class TrainerEngine:
         if not (dist.is_initialized() and dist.get_world_size() > 1):
             return
         if hasattr(self.opt, "state_buffers"):
-            # FusedAdam: m, v and the step counter
+            # FusedAdam: m, v and the step counter; FusedLARS: velocities
             for t in self.opt.state_buffers():
                 dist.broadcast(t, src=src)
         elif hasattr(self.opt, "_materialize"):
@@ -351,6 +364,22 @@ class TrainerEngine:
             mirror.copy_(flat, non_blocking=True)
 
     def _build_optimizer(self):
+        if self.optimizer == "lars":
+            from ..ops.lars import FusedLARS
+
+            named = {id(p): n for n, p in self.model.named_parameters()}
+
+            def excluded(p):
+                return ((self.no_decay_1d and p.ndim <= 1) or any(
+                    s in named.get(id(p), "") for s in self.lars_exclude))
+
+            return FusedLARS(
+                self.model.parameters(), lr=self.base_lr,
+                momentum=self.momentum, lars_coeff=self.lars_coeff,
+                lars_weight_decay=self.weight_decay, epsilon=self.lars_eps,
+                exclude=excluded, grad_scale=self.reducer.grad_scale,
+                reducer=self.reducer,
+            )
         if self.optimizer != "momentum":
             from ..ops.adam import FusedAdam
 
@@ -382,8 +411,9 @@ class TrainerEngine:
         (reference train_parameters, models/resnet_vd.py) and rescales on
         every elastic world change. adam / adamw: base_lr as it is — the
         reference's adam strategy is a constant LR with no linear scaling
-        and no piecewise decay (train_with_fleet.py:196-200)."""
-        if self.optimizer != "momentum":
+        and no piecewise decay (train_with_fleet.py:196-200). lars follows
+        the momentum schedule: the trust ratio multiplies it per tensor."""
+        if self.optimizer not in ("momentum", "lars"):
             return self.base_lr
         lr = self.base_lr * self.global_batch / 256.0
         return piecewise_lr(lr, epoch, step_in_epoch=step_in_epoch)
@@ -542,6 +572,8 @@ class TrainerEngine:
                         self.opt.grad_scale = base
                 else:
                     self.opt.step(**opt_kw)
+                if self.optimizer == "lars":
+                    self.last_trust_ratios = self.opt.trust_ratios()
             else:
                 scale = self.reducer.grad_scale * inv_scale
                 if scale != 1.0:

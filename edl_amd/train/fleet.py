@@ -40,6 +40,11 @@ class DistributedStrategy:
     # global-norm gradient clipping (Paddle: GradientClipByGlobalNorm);
     # None = off. Refused together with use_dgc.
     clip_grad_norm: float = None
+    # LARS (Paddle: strategy.lars + lars_configs). Paddle's keys:
+    # lars_coeff, lars_weight_decay, epsilon, exclude_from_weight_decay (a
+    # list of parameter-name substrings). Refused together with use_dgc.
+    lars: bool = False
+    lars_configs: dict = field(default_factory=dict)
     extra: dict = field(default_factory=dict)
 
 
@@ -96,6 +101,18 @@ def distributed_engine(model_name="resnet50_vd", strategy=None, **kwargs):
         kwargs.setdefault("dgc_rampup", cfg.get("rampup_begin_step", 0))
         kwargs.setdefault("dgc_rampup_step", cfg.get("rampup_step", 1))
         kwargs.setdefault("dgc_sparsity", cfg.get("sparsity", [0.999]))
+    if strategy.lars:
+        cfg = dict(strategy.lars_configs)
+        unknown = set(cfg) - {"lars_coeff", "lars_weight_decay", "epsilon",
+                              "exclude_from_weight_decay"}
+        if unknown:
+            raise ValueError("lars_configs: unknown keys %s" % sorted(unknown))
+        kwargs.setdefault("optimizer", "lars")
+        kwargs.setdefault("lars_coeff", cfg.get("lars_coeff", 0.001))
+        kwargs.setdefault("weight_decay", cfg.get("lars_weight_decay", 0.0005))
+        kwargs.setdefault("lars_eps", cfg.get("epsilon", 0.0))
+        kwargs.setdefault("lars_exclude",
+                          list(cfg.get("exclude_from_weight_decay", ())))
     kwargs.setdefault("recompute", strategy.use_recompute)
     kwargs.setdefault("clip_grad_norm", strategy.clip_grad_norm)
     eng = TrainerEngine(model=model_name, **kwargs)

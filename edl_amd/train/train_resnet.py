@@ -73,13 +73,18 @@ def parse_args(argv=None):
     # reference train_with_fleet.py:196-200 `adam` strategy (constant LR);
     # adamw = decoupled decay
     p.add_argument("--optimizer", default="momentum",
-                   choices=["momentum", "adam", "adamw"])
+                   choices=["momentum", "adam", "adamw", "lars"])
     p.add_argument("--beta1", type=float, default=0.9)
     p.add_argument("--beta2", type=float, default=0.999)
     p.add_argument("--epsilon", type=float, default=1e-8)
     p.add_argument("--no_decay_1d", type=int, default=0,
                    help="adam/adamw: no weight decay on biases and BN "
-                        "scale/shift (params with ndim <= 1)")
+                        "scale/shift (params with ndim <= 1); lars: those "
+                        "take the plain LR")
+    # lars: Paddle's lars_momentum; --weight_decay is the LARS decay and the
+    # LR follows the momentum schedule
+    p.add_argument("--lars_coeff", type=float, default=0.001)
+    p.add_argument("--lars_eps", type=float, default=0.0)
     p.add_argument("--clip_grad_norm", type=float, default=None,
                    help="clip the global gradient norm to this value "
                         "(device-side, capture-safe; not with --use_dgc)")
@@ -119,6 +124,8 @@ def main(argv=None):
         no_decay_1d=bool(args.no_decay_1d),
         clip_grad_norm=args.clip_grad_norm,
         skip_nonfinite=bool(args.skip_nonfinite),
+        lars_coeff=args.lars_coeff,
+        lars_eps=args.lars_eps,
     ).setup(tenv)
 
     # status reporting back to the control plane (reference TrainStatus flow,

@@ -36,7 +36,9 @@ def main(argv=None):
     # the reference trains ctr and fit_a_line with Adam
     # (example/ctr/ctr/train.py:234)
     p.add_argument("--optimizer", default="momentum",
-                   choices=["momentum", "adam"])
+                   choices=["momentum", "adam", "lars"])
+    p.add_argument("--lars_coeff", type=float, default=0.001)
+    p.add_argument("--lars_eps", type=float, default=0.0)
     p.add_argument("--clip_grad_norm", type=float, default=None,
                    help="clip the global gradient norm to this value")
     p.add_argument("--skip_nonfinite", type=int, default=0,
@@ -64,6 +66,13 @@ def main(argv=None):
         from ..ops.adam import FusedAdam
 
         opt = FusedAdam(model.parameters(), lr=args.lr,
+                        grad_scale=reducer.grad_scale, reducer=reducer)
+    elif args.optimizer == "lars":
+        from ..ops.lars import FusedLARS
+
+        opt = FusedLARS(model.parameters(), lr=args.lr, momentum=0.9,
+                        lars_coeff=args.lars_coeff, epsilon=args.lars_eps,
+                        exclude=lambda p: p.ndim <= 1,
                         grad_scale=reducer.grad_scale, reducer=reducer)
     else:
         opt = FusedSGD(model.parameters(), lr=args.lr, momentum=0.9,
