@@ -30,6 +30,18 @@ __device__ __forceinline__ float wave_reduce_sum(float v) {
   return v;
 }
 
+__device__ __forceinline__ double wave_reduce_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
+
+// acc += x^2 in double (sums of squares: grad_norm.hip, fused_lars.hip)
+__device__ __forceinline__ void sq_acc(double& acc, const float x) {
+  const double d = (double)x;
+  acc = fma(d, d, acc);
+}
+
 __device__ __forceinline__ float wave_reduce_max(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_down(v, off, 64));

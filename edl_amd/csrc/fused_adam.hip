@@ -30,12 +30,9 @@
 // Per-segment weight decay (biases / norm scales excluded from decay) stays
 // one launch: seg_end[nseg] (cumulative element ends, last == n) and
 // seg_wd[nseg] are copied to LDS once per block (8 B per segment, at most
-// kAdamMaxSegments) and looked up per ELEMENT — a float4 may straddle a
-// boundary and a segment may be shorter than a vector. nseg == 0 (null
-// tables) = uniform wd, no LDS, no lookup. Every table index is clamped to
-// nseg-1, so a malformed table mis-assigns decay but never reads outside
-// the LDS copy.
-#include "common.h"
+// kAdamMaxSegments) and looked up per element (flat_update.h). nseg == 0
+// (null tables) = uniform wd, no LDS, no lookup.
+#include "flat_update.h"
 #include "launchers.h"
 
 namespace {
@@ -59,24 +56,6 @@ __device__ __forceinline__ void adam_elem(const AdamCoef& c, const float wd,
   p = fmaf(-c.step_size, m / denom, p);
 }
 
-// first segment s in [lo, nseg) with s_end[s] > e (nseg-1 if none)
-__device__ __forceinline__ int adam_find_seg(const int* s_end, int lo,
-                                             const int nseg, const int e) {
-  int hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (s_end[mid] > e) hi = mid; else lo = mid + 1;
-  }
-  return lo;
-}
-
-// segment of element e, walking forward from s (e >= the start of s)
-__device__ __forceinline__ int adam_next_seg(const int* s_end, int s,
-                                             const int nseg, const int e) {
-  while (s + 1 < nseg && e >= s_end[s]) ++s;
-  return s;
-}
-
 }  // namespace
 
 extern "C" __global__ void fused_adam_f32(
@@ -88,9 +67,7 @@ extern "C" __global__ void fused_adam_f32(
     const int decoupled, const long long n, const int* __restrict__ seg_end,
     const float* __restrict__ seg_wd, const int nseg,
     const float* __restrict__ clip) {
-  // clip = [coef, norm, skip, nskipped] of grad_norm.hip, or null: a skipped
-  // step leaves before any store or barrier (uniform)
-  if (clip && clip[2] != 0.0f) return;
+  if (clip_skipped(clip)) return;
   extern __shared__ int s_tab[];  // [nseg] ends, then [nseg] decays
   int* s_end = s_tab;
   float* s_wd = reinterpret_cast<float*>(s_tab + nseg);
@@ -104,12 +81,11 @@ extern "C" __global__ void fused_adam_f32(
 
   // one broadcast load each, L2-resident
   AdamCoef c;
-  c.lr = lr_dev ? *lr_dev : lr_host;
+  c.lr = load_lr(lr_dev, lr_host);
   const int t = *step_dev;
   const float tf = (float)(t > 1 ? t : 1);
   c.b1 = b1; c.b2 = b2; c.omb1 = omb1; c.omb2 = omb2;
-  // coef == 1.0f is bitwise the null path
-  c.eps = eps; c.scale = clip ? scale * clip[0] : scale;
+  c.eps = eps; c.scale = clip_scale(scale, clip);
   c.decoupled = decoupled != 0;
   c.step_size = c.lr / -expm1f(tf * ln_b1);
   c.sqrt_bc2 = sqrtf(-expm1f(tf * ln_b2));
@@ -121,21 +97,17 @@ extern "C" __global__ void fused_adam_f32(
   float4* v4 = reinterpret_cast<float4*>(v);
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long stride = (long long)gridDim.x * blockDim.x;
-  int s = 0;  // segments only grow along a thread's grid-stride walk
+  int cur = 0;  // segment cursor of find_seg4
   for (; i < n4; i += stride) {
     float4 pg = g4[i], pp = p4[i], pm = m4[i], pv = v4[i];
     float w0 = wd, w1 = wd, w2 = wd, w3 = wd;
     if (nseg > 0) {
-      const int e = (int)(i << 2);  // the binding holds n < 2^31 here
-      s = adam_find_seg(s_end, s, nseg, e);
-      int q = s;
-      w0 = s_wd[q];
-      q = adam_next_seg(s_end, q, nseg, e + 1);
-      w1 = s_wd[q];
-      q = adam_next_seg(s_end, q, nseg, e + 2);
-      w2 = s_wd[q];
-      q = adam_next_seg(s_end, q, nseg, e + 3);
-      w3 = s_wd[q];
+      // the binding holds n < 2^31 here
+      const Seg4 q = find_seg4(s_end, cur, nseg, (int)(i << 2));
+      w0 = s_wd[q.q0];
+      w1 = s_wd[q.q1];
+      w2 = s_wd[q.q2];
+      w3 = s_wd[q.q3];
     }
     adam_elem(c, w0, pg.x, pp.x, pm.x, pv.x);
     adam_elem(c, w1, pg.y, pp.y, pm.y, pv.y);
@@ -149,7 +121,7 @@ extern "C" __global__ void fused_adam_f32(
   for (long long j = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x;
        j < n; j += stride) {
     float w = wd;
-    if (nseg > 0) w = s_wd[adam_find_seg(s_end, 0, nseg, (int)j)];
+    if (nseg > 0) w = s_wd[find_seg(s_end, 0, nseg, (int)j)];
     float pj = p[j], mj = m[j], vj = v[j];
     adam_elem(c, w, g[j], pj, mj, vj);
     m[j] = mj;

@@ -39,7 +39,7 @@
 // a malformed table gives wrong numbers, never an access outside the
 // buffers (the bindings check the tables once; under stream capture they
 // cannot).
-#include "common.h"
+#include "flat_update.h"
 #include "launchers.h"
 
 namespace {
@@ -48,12 +48,6 @@ constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
 constexpr int kTrustRounds = kLarsTrustPreload / kWave;
 static_assert(kLarsTrustPreload % kWave == 0, "whole 64-chunk rounds");
-
-__device__ __forceinline__ double wave_reduce_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
 
 // lane l's value in every lane, l wave-uniform: two v_readlane_b32 through
 // SGPRs, where a __shfl is a ds_bpermute round trip in every step of a
@@ -65,32 +59,9 @@ __device__ __forceinline__ double readlane_f64(const double v, const int l) {
   return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
-__device__ __forceinline__ void sq_acc(double& acc, const float x) {
-  const double d = (double)x;
-  acc = fma(d, d, acc);
-}
-
 __device__ __forceinline__ long long clampll(long long x, long long lo,
                                              long long hi) {
   return x < lo ? lo : (x > hi ? hi : x);
-}
-
-// first segment s in [lo, nseg) with s_end[s] > e (nseg-1 if none)
-__device__ __forceinline__ int lars_find_seg(const int* s_end, int lo,
-                                             const int nseg, const int e) {
-  int hi = nseg - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (s_end[mid] > e) hi = mid; else lo = mid + 1;
-  }
-  return lo;
-}
-
-// segment of element e, walking forward from s (e >= the start of s)
-__device__ __forceinline__ int lars_next_seg(const int* s_end, int s,
-                                             const int nseg, const int e) {
-  while (s + 1 < nseg && e >= s_end[s]) ++s;
-  return s;
 }
 
 // d = s*g + wd*p; v = mu*v + llr*d; p -= v  (llr = lr * trust)
@@ -200,8 +171,8 @@ extern "C" __global__ __launch_bounds__(256) void lars_trust_f32(
     }
   }
   if (lane != 0) return;
-  // the fp32 product the update kernel forms (coef == 1.0f: the null path)
-  const float s = clip ? grad_scale * clip[0] : grad_scale;
+  // the fp32 product the update kernel forms
+  const float s = clip_scale(grad_scale, clip);
   const double pn = sqrt(sp);
   const double gn = (double)s * sqrt(sg);
   double t = 1.0;
@@ -216,16 +187,13 @@ extern "C" __global__ void fused_lars_f32(
     const float* __restrict__ seg_wd, const int* __restrict__ seg_tensor,
     const int nseg, const float* __restrict__ trust, const int ntensors,
     const float* __restrict__ clip) {
-  // clip = [coef, norm, skip, nskipped] of grad_norm.hip, or null: a skipped
-  // step leaves before any store or barrier (uniform)
-  if (clip && clip[2] != 0.0f) return;
+  if (clip_skipped(clip)) return;
   extern __shared__ int s_tab[];  // [nseg] ends, [nseg] decays, [nseg] lr*trust
   int* s_end = s_tab;
   float* s_wd = reinterpret_cast<float*>(s_tab + nseg);
   float* s_lr = reinterpret_cast<float*>(s_tab + 2 * nseg);
-  // lr from the device scalar, so a captured step tracks set_lr() on replay;
-  // it meets the trust ratio HERE, not on the host
-  const float lr = lr_dev ? *lr_dev : lr_host;
+  // lr meets the trust ratio HERE, not on the host
+  const float lr = load_lr(lr_dev, lr_host);
   for (int k = threadIdx.x; k < nseg; k += blockDim.x) {
     s_end[k] = seg_end[k];
     s_wd[k] = seg_wd[k];
@@ -234,8 +202,7 @@ extern "C" __global__ void fused_lars_f32(
     s_lr[k] = lr * trust[t];
   }
   __syncthreads();
-  // coef == 1.0f is bitwise the null path
-  const float s = clip ? scale * clip[0] : scale;
+  const float s = clip_scale(scale, clip);
 
   const long long n4 = n >> 2;
   const float4* g4 = reinterpret_cast<const float4*>(g);
@@ -243,26 +210,23 @@ extern "C" __global__ void fused_lars_f32(
   float4* v4 = reinterpret_cast<float4*>(v);
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long stride = (long long)gridDim.x * blockDim.x;
-  int q0 = 0;  // segments only grow along a thread's grid-stride walk
+  int cur = 0;  // segment cursor of find_seg4
   for (; i < n4; i += stride) {
     const float4 pg = g4[i];
     float4 pp = p4[i], pv = v4[i];
-    const int e = (int)(i << 2);  // the binding holds n < 2^31
-    q0 = lars_find_seg(s_end, q0, nseg, e);
-    const int q1 = lars_next_seg(s_end, q0, nseg, e + 1);
-    const int q2 = lars_next_seg(s_end, q1, nseg, e + 2);
-    const int q3 = lars_next_seg(s_end, q2, nseg, e + 3);
-    lars_elem(s, mu, s_wd[q0], s_lr[q0], pg.x, pp.x, pv.x);
-    lars_elem(s, mu, s_wd[q1], s_lr[q1], pg.y, pp.y, pv.y);
-    lars_elem(s, mu, s_wd[q2], s_lr[q2], pg.z, pp.z, pv.z);
-    lars_elem(s, mu, s_wd[q3], s_lr[q3], pg.w, pp.w, pv.w);
+    // the binding holds n < 2^31
+    const Seg4 q = find_seg4(s_end, cur, nseg, (int)(i << 2));
+    lars_elem(s, mu, s_wd[q.q0], s_lr[q.q0], pg.x, pp.x, pv.x);
+    lars_elem(s, mu, s_wd[q.q1], s_lr[q.q1], pg.y, pp.y, pv.y);
+    lars_elem(s, mu, s_wd[q.q2], s_lr[q.q2], pg.z, pp.z, pv.z);
+    lars_elem(s, mu, s_wd[q.q3], s_lr[q.q3], pg.w, pp.w, pv.w);
     v4[i] = pv;
     p4[i] = pp;
   }
   // tail (n % 4)
   for (long long j = (n4 << 2) + (long long)blockIdx.x * blockDim.x + threadIdx.x;
        j < n; j += stride) {
-    const int q = lars_find_seg(s_end, 0, nseg, (int)j);
+    const int q = find_seg(s_end, 0, nseg, (int)j);
     float pj = p[j], vj = v[j];
     lars_elem(s, mu, s_wd[q], s_lr[q], g[j], pj, vj);
     v[j] = vj;

@@ -8,7 +8,7 @@
 //
 // Memory-bound: 3 reads + 2 writes of 4 B per element; float4-vectorized
 // (16 B/lane, guide Guideline 13), grid-stride.
-#include "common.h"
+#include "flat_update.h"
 #include "launchers.h"
 
 extern "C" __global__ void fused_sgd_f32(
@@ -16,18 +16,9 @@ extern "C" __global__ void fused_sgd_f32(
     const float lr_host, const float mu, const float wd, const float scale_in,
     const long long n, const float* __restrict__ lr_dev,
     const float* __restrict__ clip) {
-  // clip = [coef, norm, skip, nskipped] of grad_norm.hip, or null: a skipped
-  // step leaves before any store (uniform), otherwise the clip coefficient
-  // folds into the gradient scale (coef == 1.0f is bitwise the null path)
-  float scale = scale_in;
-  if (clip) {
-    if (clip[2] != 0.0f) return;
-    scale *= clip[0];
-  }
-  // lr comes from a device scalar when provided so a hipGraph-captured
-  // step picks up LR-schedule changes on replay (the host scalar would be
-  // frozen at capture time); one broadcast load, L2-resident.
-  const float lr = lr_dev ? *lr_dev : lr_host;
+  if (clip_skipped(clip)) return;
+  const float scale = clip_scale(scale_in, clip);
+  const float lr = load_lr(lr_dev, lr_host);
   const long long n4 = n >> 2;
   const float4* g4 = reinterpret_cast<const float4*>(g);
   float4* p4 = reinterpret_cast<float4*>(p);

@@ -35,12 +35,6 @@ namespace {
 constexpr int kBlock = 256;
 constexpr int kWaves = kBlock / kWave;
 
-__device__ __forceinline__ double wave_reduce_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
 // block sum in a fixed order: lanes by shuffle, then wave 0..3 in sequence;
 // valid in thread 0
 __device__ __forceinline__ double block_reduce_sum_f64(double v, double* s_w) {
@@ -54,11 +48,6 @@ __device__ __forceinline__ double block_reduce_sum_f64(double v, double* s_w) {
     for (int w = 0; w < kWaves; ++w) t += s_w[w];
   }
   return t;
-}
-
-__device__ __forceinline__ void sq_acc(double& acc, const float x) {
-  const double d = (double)x;
-  acc = fma(d, d, acc);
 }
 
 }  // namespace

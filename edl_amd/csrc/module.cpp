@@ -7,6 +7,7 @@
 #include <torch/extension.h>
 
 #include <c10/hip/HIPStream.h>
+#include <c10/util/FunctionRef.h>
 #include <hip/hip_runtime.h>
 
 #include "launchers.h"  // every launcher of the .hip translation units
@@ -221,79 +222,143 @@ float* clip_state_ptr(const c10::optional<torch::Tensor>& st,
   return st->data_ptr<float>();
 }
 
+// ---- flat-bucket update kernels (fused_sgd/adam/lars.hip): shared checks --
+
+// p, g and the state buffers of one bucket: GPU, fp32, contiguous, equal
+// numel, one device, 16-byte aligned (the kernels walk them as float4)
+// -> numel
+long long check_flat_f32(const char* who,
+                         std::initializer_list<const torch::Tensor*> ts) {
+  const torch::Tensor& p = **ts.begin();
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->is_cuda(), who, ": GPU tensors required");
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->scalar_type() == torch::kFloat32, who, ": fp32 only");
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->is_contiguous(), who,
+                ": contiguous flat buffers required");
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->numel() == p.numel(), who, ": size mismatch");
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(t->device() == p.device(), who,
+                ": the flat buffers must share a device");
+  for (const torch::Tensor* t : ts)
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, who,
+                ": the flat buffers must be 16-byte aligned (float4)");
+  return (long long)p.numel();
+}
+
+// optional fp32 LR scalar on `like`'s device -> pointer or null
+const float* lr_dev_ptr(const c10::optional<torch::Tensor>& lr_dev,
+                        const torch::Tensor& like, const char* who) {
+  if (!lr_dev.has_value()) return nullptr;
+  TORCH_CHECK(lr_dev->is_cuda() && lr_dev->device() == like.device() &&
+                  lr_dev->scalar_type() == torch::kFloat32 &&
+                  lr_dev->numel() == 1,
+              who, ": lr_dev must be a fp32 GPU scalar");
+  return lr_dev->data_ptr<float>();
+}
+
+// A table that lives on the device costs a D2H sync to check: a table
+// TENSOR is checked on its first eager launch and again whenever its
+// version counter or `key` (the extent it was checked against) changes.
+// The record holds a weak reference to the tensor (which pins the tensor's
+// header, never its storage), so a record cannot pass for a new tensor that
+// lands on the same address, and the kind of check that passed, so a tensor
+// checked as one table cannot pass for another. A launch under stream
+// capture cannot sync and skips the check: the optimizers check the host
+// lists they build their tables from, and the kernels clamp every table
+// value, so even an unchecked table cannot read out of bounds.
+enum class TableKind { kSegEnd, kSegTensor, kLarsChunks, kLarsTensorChunks };
+
+struct TableSeen {
+  c10::weak_intrusive_ptr<c10::TensorImpl> impl;
+  uint32_t version;
+  long long key;
+  TableKind kind;
+};
+
+void check_device_table(
+    const torch::Tensor& table, TableKind kind, long long key,
+    const char* who, c10::function_ref<void(const int*, int64_t)> check) {
+  static std::mutex mu;
+  static std::unordered_map<const c10::TensorImpl*, TableSeen> seen;
+  std::lock_guard<std::mutex> lock(mu);
+  const c10::TensorImpl* id = table.unsafeGetTensorImpl();
+  const uint32_t version = table._version();
+  auto it = seen.find(id);
+  // a live weak reference pins the TensorImpl's address: same id, same
+  // tensor
+  if (it != seen.end() && !it->second.impl.expired() &&
+      it->second.version == version && it->second.key == key &&
+      it->second.kind == kind)
+    return;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess, who,
+              ": hipStreamIsCapturing failed");
+  if (cap != hipStreamCaptureStatusNone) return;
+  auto host = table.cpu();
+  check(host.data_ptr<int>(), host.numel());
+  for (auto e = seen.begin(); e != seen.end();)  // drop dead tensors' records
+    e = e->second.impl.expired() ? seen.erase(e) : std::next(e);
+  seen.insert_or_assign(
+      id, TableSeen{c10::weak_intrusive_ptr<c10::TensorImpl>(
+                        table.getIntrusivePtr()),
+                    version, key, kind});
+}
+
+// The per-bucket segment table of fused_adam / fused_lars over a bucket of
+// n elements: seg_end (int32, cumulative ends, last == n) and seg_wd (fp32)
+// come together or not at all, seg_tensor (int32) only with them -> the
+// number of segments, 0 without a table
+int check_seg_table(const char* who, const torch::Tensor& p, long long n,
+                    const torch::Tensor* seg_end, const torch::Tensor* seg_wd,
+                    const torch::Tensor* seg_tensor = nullptr) {
+  TORCH_CHECK((seg_end != nullptr) == (seg_wd != nullptr), who,
+              ": seg_end and seg_wd come together");
+  if (seg_end == nullptr) return 0;
+  for (const torch::Tensor* t : {seg_end, seg_wd, seg_tensor})
+    TORCH_CHECK(t == nullptr ||
+                    (t->is_cuda() && t->device() == p.device() &&
+                     t->is_contiguous() && t->dim() == 1 &&
+                     t->scalar_type() ==
+                         (t == seg_wd ? torch::kFloat32 : torch::kInt32)),
+                who, ": seg_end, seg_tensor int32 / seg_wd fp32 flat GPU "
+                     "tensors on the buffers' device");
+  const int64_t nseg = seg_end->numel();
+  TORCH_CHECK(seg_wd->numel() == nseg &&
+                  (seg_tensor == nullptr || seg_tensor->numel() == nseg),
+              who, ": seg_end, seg_wd, seg_tensor differ in length");
+  TORCH_CHECK(nseg >= 1 && nseg <= kAdamMaxSegments, who,
+              ": 1 <= segments <= ", kAdamMaxSegments, " per bucket (got ",
+              nseg, ")");
+  TORCH_CHECK(n < (1LL << 31), who, ": a segment table needs numel < 2^31");
+  check_device_table(*seg_end, TableKind::kSegEnd, n, who,
+                     [&](const int* e, int64_t cnt) {
+    int prev = 0;
+    for (int64_t k = 0; k < cnt; ++k) {
+      TORCH_CHECK(e[k] >= prev, who, ": seg_end must not decrease");
+      prev = e[k];
+    }
+    TORCH_CHECK(prev == n, who, ": last seg_end (", prev,
+                ") must equal numel (", n, ")");
+  });
+  return (int)nseg;
+}
+
 void fused_sgd(torch::Tensor p, torch::Tensor g, torch::Tensor m, double lr,
                double momentum, double weight_decay, double grad_scale,
                c10::optional<torch::Tensor> lr_dev,
                c10::optional<torch::Tensor> clip_state) {
-  TORCH_CHECK(p.is_cuda() && g.is_cuda() && m.is_cuda(), "fused_sgd: GPU tensors required");
-  TORCH_CHECK(p.scalar_type() == torch::kFloat32 && g.scalar_type() == torch::kFloat32 &&
-                  m.scalar_type() == torch::kFloat32,
-              "fused_sgd: fp32 only");
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous(),
-              "fused_sgd: contiguous flat buffers required");
-  TORCH_CHECK(p.numel() == g.numel() && p.numel() == m.numel(), "fused_sgd: size mismatch");
-  const float* lrp = nullptr;
-  if (lr_dev.has_value()) {
-    TORCH_CHECK(lr_dev->is_cuda() && lr_dev->scalar_type() == torch::kFloat32 &&
-                    lr_dev->numel() == 1,
-                "fused_sgd: lr_dev must be a fp32 GPU scalar");
-    lrp = lr_dev->data_ptr<float>();
-  }
+  const long long n = check_flat_f32("fused_sgd", {&p, &g, &m});
   launch_fused_sgd_f32(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                        (float)lr, (float)momentum, (float)weight_decay,
-                       (float)grad_scale, (long long)p.numel(), lrp,
+                       (float)grad_scale, n, lr_dev_ptr(lr_dev, p, "fused_sgd"),
                        clip_state_ptr(clip_state, p, "fused_sgd"),
                        cur_stream());
 }
 
 // ---- fused Adam / AdamW (fused_adam.hip) ---------------------------------
-
-// The decay table lives on the device, so checking it costs a D2H sync: a
-// table TENSOR is checked on its first eager launch and again whenever its
-// version counter or n changes. The record holds a weak reference to the
-// tensor (which pins the tensor's header, never its storage), so a record
-// cannot pass for a new tensor that lands on the same address. A launch under stream capture cannot
-// sync and skips the check (FusedAdam checks its tables on the host when it
-// builds them); the kernel clamps every table index, so even an unchecked
-// table cannot read out of bounds.
-struct AdamTableSeen {
-  c10::weak_intrusive_ptr<c10::TensorImpl> impl;
-  uint32_t version;
-  long long n;
-};
-
-void adam_check_table(const torch::Tensor& seg_end, long long n) {
-  static std::mutex mu;
-  static std::unordered_map<const c10::TensorImpl*, AdamTableSeen> seen;
-  std::lock_guard<std::mutex> lock(mu);
-  const c10::TensorImpl* key = seg_end.unsafeGetTensorImpl();
-  const uint32_t version = seg_end._version();
-  auto it = seen.find(key);
-  // a live weak reference pins the TensorImpl's address: same key, same
-  // tensor
-  if (it != seen.end() && !it->second.impl.expired() &&
-      it->second.version == version && it->second.n == n)
-    return;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess,
-              "fused_adam: hipStreamIsCapturing failed");
-  if (cap != hipStreamCaptureStatusNone) return;
-  auto host = seg_end.cpu();
-  const int* e = host.data_ptr<int>();
-  int prev = 0;
-  for (int64_t k = 0; k < host.numel(); ++k) {
-    TORCH_CHECK(e[k] >= prev, "fused_adam: seg_end must not decrease");
-    prev = e[k];
-  }
-  TORCH_CHECK(prev == n, "fused_adam: last seg_end (", prev,
-              ") must equal numel (", n, ")");
-  for (auto e = seen.begin(); e != seen.end();)  // drop dead tensors' records
-    e = e->second.impl.expired() ? seen.erase(e) : std::next(e);
-  seen.insert_or_assign(
-      key, AdamTableSeen{c10::weak_intrusive_ptr<c10::TensorImpl>(
-                             seg_end.getIntrusivePtr()),
-                         version, n});
-}
 
 void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                 torch::Tensor v, torch::Tensor step_dev, double lr,
@@ -303,66 +368,19 @@ void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                 c10::optional<torch::Tensor> seg_end,
                 c10::optional<torch::Tensor> seg_wd,
                 c10::optional<torch::Tensor> clip_state) {
-  TORCH_CHECK(p.is_cuda() && g.is_cuda() && m.is_cuda() && v.is_cuda(),
-              "fused_adam: GPU tensors required");
-  TORCH_CHECK(p.scalar_type() == torch::kFloat32 &&
-                  g.scalar_type() == torch::kFloat32 &&
-                  m.scalar_type() == torch::kFloat32 &&
-                  v.scalar_type() == torch::kFloat32,
-              "fused_adam: fp32 only");
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && m.is_contiguous() &&
-                  v.is_contiguous(),
-              "fused_adam: contiguous flat buffers required");
-  const long long n = p.numel();
-  TORCH_CHECK(g.numel() == n && m.numel() == n && v.numel() == n,
-              "fused_adam: size mismatch");
-  TORCH_CHECK(g.device() == p.device() && m.device() == p.device() &&
-                  v.device() == p.device(),
-              "fused_adam: p, g, m, v must share a device");
-  for (const torch::Tensor* t : {&p, &g, &m, &v})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                "fused_adam: p, g, m, v must be 16-byte aligned (float4)");
+  const long long n = check_flat_f32("fused_adam", {&p, &g, &m, &v});
   TORCH_CHECK(step_dev.is_cuda() && step_dev.device() == p.device() &&
                   step_dev.scalar_type() == torch::kInt32 &&
                   step_dev.numel() == 1,
               "fused_adam: step_dev must be an int32 GPU scalar");
   TORCH_CHECK(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0,
               "fused_adam: betas must lie in [0, 1)");
-  const float* lrp = nullptr;
-  if (lr_dev.has_value()) {
-    TORCH_CHECK(lr_dev->is_cuda() && lr_dev->device() == p.device() &&
-                    lr_dev->scalar_type() == torch::kFloat32 &&
-                    lr_dev->numel() == 1,
-                "fused_adam: lr_dev must be a fp32 GPU scalar");
-    lrp = lr_dev->data_ptr<float>();
-  }
-  const int* endp = nullptr;
-  const float* wdp = nullptr;
-  int nseg = 0;
-  TORCH_CHECK(seg_end.has_value() == seg_wd.has_value(),
-              "fused_adam: seg_end and seg_wd come together");
-  if (seg_end.has_value()) {
-    TORCH_CHECK(seg_end->is_cuda() && seg_wd->is_cuda() &&
-                    seg_end->device() == p.device() &&
-                    seg_wd->device() == p.device() &&
-                    seg_end->scalar_type() == torch::kInt32 &&
-                    seg_wd->scalar_type() == torch::kFloat32 &&
-                    seg_end->is_contiguous() && seg_wd->is_contiguous() &&
-                    seg_end->dim() == 1 && seg_wd->dim() == 1,
-                "fused_adam: seg_end int32 / seg_wd fp32 flat GPU tensors");
-    TORCH_CHECK(seg_end->numel() == seg_wd->numel(),
-                "fused_adam: seg_end and seg_wd differ in length");
-    TORCH_CHECK(seg_end->numel() >= 1 &&
-                    seg_end->numel() <= kAdamMaxSegments,
-                "fused_adam: 1 <= segments <= ", kAdamMaxSegments,
-                " per bucket (got ", seg_end->numel(), ")");
-    TORCH_CHECK(n < (1LL << 31),
-                "fused_adam: a segment table needs numel < 2^31");
-    adam_check_table(*seg_end, n);
-    endp = seg_end->data_ptr<int>();
-    wdp = seg_wd->data_ptr<float>();
-    nseg = (int)seg_end->numel();
-  }
+  const float* lrp = lr_dev_ptr(lr_dev, p, "fused_adam");
+  const int nseg = check_seg_table(
+      "fused_adam", p, n, seg_end.has_value() ? &*seg_end : nullptr,
+      seg_wd.has_value() ? &*seg_wd : nullptr);
+  const int* endp = nseg ? seg_end->data_ptr<int>() : nullptr;
+  const float* wdp = nseg ? seg_wd->data_ptr<float>() : nullptr;
   const float* clipp = clip_state_ptr(clip_state, p, "fused_adam");
   if (n == 0) return;
   // 1-b and ln b in double: the float forms lose ~6e-5 relative on 1-b2
@@ -450,37 +468,6 @@ void grad_clip_finalize(torch::Tensor partial, int64_t rows_total,
 
 // ---- fused LARS (fused_lars.hip) ------------------------------------------
 
-// A device table is checked with a D2H copy on its first eager launch and
-// again whenever its version counter or `key` changes (the scheme of
-// adam_check_table, weak reference included). Under stream capture the copy
-// is impossible and the check is skipped: FusedLARS checks the host lists it
-// builds the tables from, and the kernels clamp every table value.
-template <typename F>
-void lars_check_table(const torch::Tensor& table, long long key,
-                      const char* who, F check) {
-  static std::mutex mu;
-  static std::unordered_map<const c10::TensorImpl*, AdamTableSeen> seen;
-  std::lock_guard<std::mutex> lock(mu);
-  const c10::TensorImpl* id = table.unsafeGetTensorImpl();
-  const uint32_t version = table._version();
-  auto it = seen.find(id);
-  if (it != seen.end() && !it->second.impl.expired() &&
-      it->second.version == version && it->second.n == key)
-    return;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  TORCH_CHECK(hipStreamIsCapturing(cur_stream(), &cap) == hipSuccess, who,
-              ": hipStreamIsCapturing failed");
-  if (cap != hipStreamCaptureStatusNone) return;
-  auto host = table.cpu();
-  check(host.data_ptr<int>(), host.numel());
-  for (auto e = seen.begin(); e != seen.end();)  // drop dead tensors' records
-    e = e->second.impl.expired() ? seen.erase(e) : std::next(e);
-  seen.insert_or_assign(
-      id, AdamTableSeen{c10::weak_intrusive_ptr<c10::TensorImpl>(
-                            table.getIntrusivePtr()),
-                        version, key});
-}
-
 void lars_check_int_table(const torch::Tensor& t, const torch::Tensor& like,
                           const char* who, const char* what) {
   TORCH_CHECK(t.is_cuda() && t.device() == like.device() &&
@@ -536,7 +523,8 @@ int64_t lars_sumsq(std::vector<torch::Tensor> ps, std::vector<torch::Tensor> gs,
                 "lars_sumsq: p and g of a bucket must agree, numel < 2^31");
     total += (long long)ps[b].numel();
   }
-  lars_check_table(chunks, total, "lars_sumsq", [&](const int* e, int64_t) {
+  check_device_table(chunks, TableKind::kLarsChunks, total, "lars_sumsq",
+                     [&](const int* e, int64_t) {
     int prev = 0;
     for (int64_t c = 0; c < nchunks; ++c, e += kLarsChunkFields) {
       TORCH_CHECK(e[0] >= prev && e[0] < (int64_t)nb &&
@@ -598,8 +586,8 @@ void lars_trust(torch::Tensor partial, int64_t nchunks,
               "least ntensors slots on partial's device");
   TORCH_CHECK(lars_coeff >= 0.0 && lars_weight_decay >= 0.0 && epsilon >= 0.0,
               "lars_trust: lars_coeff, lars_weight_decay, epsilon >= 0");
-  lars_check_table(tensor_chunks, nchunks, "lars_trust",
-                   [&](const int* e, int64_t) {
+  check_device_table(tensor_chunks, TableKind::kLarsTensorChunks, nchunks,
+                     "lars_trust", [&](const int* e, int64_t) {
     for (int64_t k = 0; k < nt; ++k, e += 2)
       TORCH_CHECK(e[0] >= 0 && e[1] >= 0 && (int64_t)e[0] + e[1] <= nchunks,
                   "lars_trust: tensor ", k, " owns chunks [", e[0], ", +",
@@ -618,63 +606,21 @@ void fused_lars(torch::Tensor p, torch::Tensor g, torch::Tensor v, double lr,
                 torch::Tensor seg_wd, torch::Tensor seg_tensor,
                 torch::Tensor trust, c10::optional<torch::Tensor> lr_dev,
                 c10::optional<torch::Tensor> clip_state) {
-  TORCH_CHECK(p.is_cuda() && g.is_cuda() && v.is_cuda(),
-              "fused_lars: GPU tensors required");
-  TORCH_CHECK(p.scalar_type() == torch::kFloat32 &&
-                  g.scalar_type() == torch::kFloat32 &&
-                  v.scalar_type() == torch::kFloat32,
-              "fused_lars: fp32 only");
-  TORCH_CHECK(p.is_contiguous() && g.is_contiguous() && v.is_contiguous(),
-              "fused_lars: contiguous flat buffers required");
-  const long long n = p.numel();
-  TORCH_CHECK(g.numel() == n && v.numel() == n, "fused_lars: size mismatch");
-  TORCH_CHECK(g.device() == p.device() && v.device() == p.device(),
-              "fused_lars: p, g, v must share a device");
-  for (const torch::Tensor* t : {&p, &g, &v})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
-                "fused_lars: p, g, v must be 16-byte aligned (float4)");
-  TORCH_CHECK(n < (1LL << 31), "fused_lars: the segment table needs numel < "
-                               "2^31");
-  const float* lrp = nullptr;
-  if (lr_dev.has_value()) {
-    TORCH_CHECK(lr_dev->is_cuda() && lr_dev->device() == p.device() &&
-                    lr_dev->scalar_type() == torch::kFloat32 &&
-                    lr_dev->numel() == 1,
-                "fused_lars: lr_dev must be a fp32 GPU scalar");
-    lrp = lr_dev->data_ptr<float>();
-  }
+  const long long n = check_flat_f32("fused_lars", {&p, &g, &v});
+  const float* lrp = lr_dev_ptr(lr_dev, p, "fused_lars");
+  // 16-byte aligned int tables, as fused_lars (not fused_adam) asks
   lars_check_int_table(seg_end, p, "fused_lars", "seg_end");
   lars_check_int_table(seg_tensor, p, "fused_lars", "seg_tensor");
-  TORCH_CHECK(seg_wd.is_cuda() && seg_wd.device() == p.device() &&
-                  seg_wd.scalar_type() == torch::kFloat32 &&
-                  seg_wd.is_contiguous(),
-              "fused_lars: seg_wd must be a contiguous fp32 tensor on the "
-              "buffers' device");
-  const int64_t nseg = seg_end.numel();
-  TORCH_CHECK(seg_end.dim() == 1 && seg_wd.dim() == 1 &&
-                  seg_tensor.dim() == 1 && seg_wd.numel() == nseg &&
-                  seg_tensor.numel() == nseg,
-              "fused_lars: seg_end, seg_wd, seg_tensor differ in length");
-  TORCH_CHECK(nseg >= 1 && nseg <= kAdamMaxSegments,
-              "fused_lars: 1 <= segments <= ", kAdamMaxSegments,
-              " per bucket (got ", nseg, ")");
+  const int nseg =
+      check_seg_table("fused_lars", p, n, &seg_end, &seg_wd, &seg_tensor);
   TORCH_CHECK(trust.is_cuda() && trust.device() == p.device() &&
                   trust.scalar_type() == torch::kFloat32 &&
                   trust.is_contiguous() && trust.numel() >= 1 &&
                   trust.numel() < (1LL << 31),
               "fused_lars: trust must be a non-empty contiguous fp32 tensor "
               "on the buffers' device");
-  lars_check_table(seg_end, n, "fused_lars", [&](const int* e, int64_t cnt) {
-    int prev = 0;
-    for (int64_t k = 0; k < cnt; ++k) {
-      TORCH_CHECK(e[k] >= prev, "fused_lars: seg_end must not decrease");
-      prev = e[k];
-    }
-    TORCH_CHECK(prev == n, "fused_lars: last seg_end (", prev,
-                ") must equal numel (", n, ")");
-  });
-  lars_check_table(seg_tensor, trust.numel(), "fused_lars",
-                   [&](const int* e, int64_t cnt) {
+  check_device_table(seg_tensor, TableKind::kSegTensor, trust.numel(),
+                     "fused_lars", [&](const int* e, int64_t cnt) {
     for (int64_t k = 0; k < cnt; ++k)
       TORCH_CHECK(e[k] >= 0 && e[k] < trust.numel(),
                   "fused_lars: seg_tensor[", k, "] = ", e[k],
@@ -686,7 +632,7 @@ void fused_lars(torch::Tensor p, torch::Tensor g, torch::Tensor v, double lr,
                         v.data_ptr<float>(), lrp, (float)lr, (float)momentum,
                         (float)grad_scale, n, seg_end.data_ptr<int>(),
                         seg_wd.data_ptr<float>(), seg_tensor.data_ptr<int>(),
-                        (int)nseg, trust.data_ptr<float>(),
+                        nseg, trust.data_ptr<float>(),
                         (int)trust.numel(), clipp, cur_stream());
 }
 

@@ -14,17 +14,13 @@ step counter, which step() advances with a captured op and the kernel turns
 into bias corrections itself — so a hipGraph-captured step keeps counting
 on replay, where no host code runs. On GPU that counter is the source of
 truth (state_dict() reads it back); on CPU the same tensor lives on the
-host and the update is the torch op sequence of torch.optim.Adam. Buckets
-on a GPU ALWAYS take the kernel: without the built extension step() raises
-(ops.ext()) instead of running the torch math there — unlike FusedSGD's
-`_use_ext` switch, on purpose: a missing kernel is an error in this
-project, not a slower path taken quietly.
+host and the update is the torch op sequence of torch.optim.Adam.
 
 no_decay (None | predicate param -> bool | iterable of params) exempts
 params from weight decay. Adjacent params of a bucket with equal decay
 coalesce into one segment of the kernel's decay table; a bucket whose
-params all agree needs no table. The kernel takes at most
-ADAM_MAX_SEGMENTS (1024) segments per bucket.
+params all agree needs no table. The kernel takes at most MAX_SEGMENTS
+(1024) segments per bucket.
 
 State-dict format matches torch.optim.Adam (per-param step / exp_avg /
 exp_avg_sq, indexed in the order the params were given), so checkpoints
@@ -32,13 +28,20 @@ interchange with torch and survive re-bucketing across elastic resizes."""
 import torch
 
 from . import ext
-from ..train.bucketed_ddp import _view_like
+from .flat_optimizer import MAX_SEGMENTS, FlatBucketOptimizer
 
-ADAM_MAX_SEGMENTS = 1024  # == _C.ADAM_MAX_SEGMENTS (csrc/launchers.h)
+ADAM_MAX_SEGMENTS = MAX_SEGMENTS
 
 
-class FusedAdam:
-    handles_grad_scale = True
+class FusedAdam(FlatBucketOptimizer):
+    _name = "FusedAdam"
+    _state_names = ("m", "v")
+    _state_keys = {"exp_avg": "m", "exp_avg_sq": "v"}
+    _hyper_keys = ("lr", "eps", "weight_decay", "betas")
+    _select_key = "no_decay"
+    _table_kind = "decay"
+    _cap_message = ("a bucket alternates decay %d times; the kernel's table "
+                    "holds %d segments per bucket (use a smaller bucket cap)")
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8,
                  weight_decay=0.0, decoupled=False, no_decay=None,
@@ -48,119 +51,33 @@ class FusedAdam:
             raise ValueError("FusedAdam: betas must lie in [0, 1)")
         if eps < 0.0 or lr < 0.0 or weight_decay < 0.0:
             raise ValueError("FusedAdam: lr, eps, weight_decay must be >= 0")
-        # state-dict indices follow the order given, as torch.optim does
-        self._all_params = list(params)
-        self._index = {id(p): i for i, p in enumerate(self._all_params)}
-        if no_decay is None:
-            nd = []
-        elif callable(no_decay):
-            nd = [i for i, p in enumerate(self._all_params) if no_decay(p)]
-        else:
-            ids = {id(p) for p in no_decay}
-            nd = [i for i, p in enumerate(self._all_params) if id(p) in ids]
-        self._no_decay = set(nd)
-        self.defaults = dict(lr=float(lr), betas=betas, eps=float(eps),
-                             weight_decay=float(weight_decay), amsgrad=False,
-                             decoupled=bool(decoupled), no_decay=sorted(nd))
-        self.param_groups = [dict(
-            self.defaults,
-            params=[p for p in self._all_params if p.requires_grad])]
-        self.grad_scale = grad_scale
-        self._reducer = reducer
-        self._buckets = None
         # int32 [1] on the buckets' device: THE step count (see module doc)
         self._step_t = None
-        # LR device scalar on GPU, read by the kernel at run time so a
-        # captured step tracks set_lr() on replay
-        self._lr_dev = None
-        if reducer is not None:
-            self.attach(reducer)
-
-    def attach(self, reducer):
-        self._reducer = reducer
-        self._buckets = None
-        reducer._attached_opt = self  # rebuild() snapshots/restores m, v, step
-        return self
-
-    def set_lr(self, lr):
-        """Set the learning rate (updates the device scalar when present)."""
-        for g in self.param_groups:
-            g["lr"] = float(lr)
-        if self._lr_dev is not None:
-            self._lr_dev.fill_(float(lr))
+        super().__init__(
+            params,
+            dict(lr=float(lr), betas=betas, eps=float(eps),
+                 weight_decay=float(weight_decay), amsgrad=False,
+                 decoupled=bool(decoupled)),
+            select=no_decay, grad_scale=grad_scale, reducer=reducer)
 
     @property
     def step_count(self):
         """Optimizer steps taken (reads the device counter back on GPU)."""
         return 0 if self._step_t is None else int(self._step_t.item())
 
-    def _param_wd(self, p):
-        wd = self.param_groups[0]["weight_decay"]
-        return 0.0 if self._index.get(id(p)) in self._no_decay else wd
-
     def _build_tables(self):
         """Per bucket: coalesce adjacent params of equal decay into
         segments; one segment = uniform decay, no table."""
         for bk in self._buckets:
-            segs = []  # [end, wd]
-            for (off, n), p in zip(bk["offsets"], bk["params"]):
-                wd = self._param_wd(p)
-                if segs and segs[-1][1] == wd:
-                    segs[-1][0] = off + n
-                else:
-                    segs.append([off + n, wd])
-            bk["segs"] = segs
+            self._build_segments(bk, merge=lambda prev, wd: prev == wd)
+            segs = bk["segs"]
             bk["wd"] = segs[0][1] if len(segs) == 1 else 0.0
-            bk["seg_end"] = bk["seg_wd"] = None
-            if len(segs) > 1 and bk["p"].is_cuda:
-                if len(segs) > ADAM_MAX_SEGMENTS:
-                    raise RuntimeError(
-                        "FusedAdam: a bucket alternates decay %d times; the "
-                        "kernel's table holds %d segments per bucket (use a "
-                        "smaller bucket cap)" % (len(segs), ADAM_MAX_SEGMENTS))
-                # checked HERE, on the host lists: the binding can only
-                # check a device table with a D2H sync, which it cannot
-                # afford under graph capture
-                ends = [s[0] for s in segs]
-                if (ends != sorted(ends) or ends[-1] != bk["p"].numel()
-                        or bk["p"].numel() >= 2 ** 31):
-                    raise RuntimeError("FusedAdam: malformed decay table")
-                dev = bk["p"].device
-                bk["seg_end"] = torch.tensor([s[0] for s in segs],
-                                             dtype=torch.int32, device=dev)
-                bk["seg_wd"] = torch.tensor([s[1] for s in segs],
-                                            dtype=torch.float32, device=dev)
 
-    def _materialize(self):
-        if self._buckets is not None:
-            return self._buckets
-        r = self._reducer
-        if r is None:
-            raise RuntimeError("FusedAdam needs a BucketedAllReducer (call attach())")
-        out = []
-        for b in r._buckets:
-            if b.param_flat is None:
-                raise RuntimeError("FusedAdam requires flatten_params=True buckets")
-            offsets = []
-            off = 0
-            for p in b.params:
-                offsets.append((off, p.numel()))
-                off += p.numel()
-            out.append({"p": b.param_flat, "g": b.buffer,
-                        "m": torch.zeros_like(b.param_flat),
-                        "v": torch.zeros_like(b.param_flat),
-                        "params": b.params, "offsets": offsets})
-        self._buckets = out
+    def _on_materialize(self, buckets):
         self._build_tables()
-        if out:
-            dev = out[0]["p"].device
-            if self._step_t is None:  # survives rebuild(): m, v do not
-                self._step_t = torch.zeros(1, dtype=torch.int32, device=dev)
-            if dev.type == "cuda" and self._lr_dev is None:
-                self._lr_dev = torch.full(
-                    (1,), self.param_groups[0]["lr"], dtype=torch.float32,
-                    device=dev)
-        return out
+        if buckets and self._step_t is None:  # survives rebuild(): m, v do not
+            self._step_t = torch.zeros(1, dtype=torch.int32,
+                                       device=buckets[0]["p"].device)
 
     @torch.no_grad()
     def step(self, clip_state=None):
@@ -202,12 +119,7 @@ class FusedAdam:
         bc2_sqrt = bc2 ** 0.5
         for bk in buckets:
             p, m, v = bk["p"], bk["m"], bk["v"]
-            g = bk["g"]
-            if clip_state is not None:
-                # fp32 product first, as the kernel forms it
-                g = g.mul(clip_state[0] * self.grad_scale)
-            elif self.grad_scale != 1.0:
-                g = g.mul(self.grad_scale)
+            g = self._cpu_grad(bk, clip_state)
             start = 0
             for end, wd in bk["segs"]:
                 if wd != 0.0:
@@ -223,87 +135,39 @@ class FusedAdam:
             denom = (v.sqrt() / bc2_sqrt).add_(eps)
             p.addcdiv_(m, denom, value=-step_size)
 
-    def zero_grad(self, set_to_none=False):
-        if self._reducer is not None:
-            self._reducer.zero_grad()
-
     def state_buffers(self):
-        """Every tensor that must agree across ranks: m, v per bucket and
-        the step counter (the engine broadcasts them from rank 0)."""
-        out = []
-        for bk in self._materialize():
-            out += [bk["m"], bk["v"]]
+        """m, v per bucket and the step counter."""
+        out = super().state_buffers()
         if self._step_t is not None:
             out.append(self._step_t)
         return out
 
     # ---- torch.optim.Adam-compatible state dict ----
-    def state_dict(self):
-        state = {}
-        buckets = self._materialize()
-        t = float(self.step_count)
-        for bk in buckets:
-            for (off, n), p in zip(bk["offsets"], bk["params"]):
-                state[self._index[id(p)]] = {
-                    "step": torch.tensor(t, dtype=torch.float32),
-                    "exp_avg": _view_like(bk["m"][off:off + n], p).clone(),
-                    "exp_avg_sq": _view_like(bk["v"][off:off + n], p).clone(),
-                }
-        state = {k: state[k] for k in sorted(state)}
-        groups = [{k: v for k, v in self.param_groups[0].items() if k != "params"}]
-        groups[0]["no_decay"] = sorted(self._no_decay)
-        groups[0]["params"] = list(range(len(self._all_params)))
-        return {"state": state, "param_groups": groups}
+    def _state_entry(self):
+        return {"step": torch.tensor(float(self.step_count),
+                                     dtype=torch.float32)}
 
     def load_state_dict(self, sd):
         """The moments, the step, lr, betas, eps and weight_decay are taken
         from `sd`. The decay MODE (`decoupled`, the `no_decay` set) is this
         optimizer's construction-time choice: a state dict that records
         another one (torch's own records neither) is refused with a
-        ValueError before anything is loaded, rather than silently changing
-        what weight decay means mid-run."""
-        if sd.get("param_groups"):
-            src = sd["param_groups"][0]
-            if ("decoupled" in src
-                    and bool(src["decoupled"]) != self.param_groups[0]["decoupled"]):
-                raise ValueError(
-                    "FusedAdam: state dict was saved with decoupled=%s, this "
-                    "optimizer has decoupled=%s" % (
-                        bool(src["decoupled"]),
-                        self.param_groups[0]["decoupled"]))
-            if ("no_decay" in src
-                    and sorted(src["no_decay"]) != sorted(self._no_decay)):
-                raise ValueError(
-                    "FusedAdam: state dict exempts params %s from weight "
-                    "decay, this optimizer %s" % (
-                        sorted(src["no_decay"]), sorted(self._no_decay)))
-        state = sd.get("state", {})
-        steps = []
-        for bk in self._materialize():
-            for (off, n), p in zip(bk["offsets"], bk["params"]):
-                idx = self._index[id(p)]
-                ent = state.get(idx, state.get(str(idx)))
-                if not ent:
-                    continue
-                for key, flat in (("exp_avg", bk["m"]), ("exp_avg_sq", bk["v"])):
-                    if ent.get(key) is not None:
-                        _view_like(flat[off:off + n], p).copy_(
-                            ent[key].to(flat.device))
-                if ent.get("step") is not None:
-                    steps.append(int(float(ent["step"])))
+        ValueError before anything is loaded."""
+        src = sd["param_groups"][0] if sd.get("param_groups") else {}
+        mine = self.param_groups[0]["decoupled"]
+        if "decoupled" in src and bool(src["decoupled"]) != mine:
+            raise ValueError(
+                "FusedAdam: state dict was saved with decoupled=%s, this "
+                "optimizer has decoupled=%s" % (bool(src["decoupled"]), mine))
+        super().load_state_dict(sd)
+
+    def _on_load(self, entries, changed):
+        steps = [int(float(e["step"])) for e in entries
+                 if e.get("step") is not None]
         if steps and self._step_t is not None:
             # one shared counter: every param steps together here
             self._step_t.fill_(max(steps))
-        if sd.get("param_groups"):
-            src = sd["param_groups"][0]
-            g0 = self.param_groups[0]
-            for k in ("lr", "eps", "weight_decay"):
-                if k in src:
-                    g0[k] = float(src[k])
-            if "betas" in src:
-                g0["betas"] = (float(src["betas"][0]), float(src["betas"][1]))
-            if self._lr_dev is not None:
-                self._lr_dev.fill_(g0["lr"])
+        if changed is not None:
             self._build_tables()  # weight_decay may have changed
 
 

@@ -121,9 +121,10 @@ class BucketedAllReducer:
 
     def rebuild(self, bucket_cap_mb):
         """Re-bucket (e.g. after an elastic resize changed the optimal
-        chunk size). Gradients are re-viewed into fresh buffers. An
-        attached FusedSGD's momentum is snapshotted per-param and restored
-        into the new bucket layout, and on_rebuild callbacks (e.g. the
+        chunk size). Gradients are re-viewed into fresh buffers. The state
+        of an attached flat-bucket optimizer (FusedSGD, FusedAdam,
+        FusedLARS) is snapshotted per-param through its state dict and
+        restored into the new bucket layout, and on_rebuild callbacks (e.g. the
         engine's bf16-mirror rebuild) fire afterwards — without this the
         optimizer would keep updating the DEAD flat buffers and training
         would silently stop progressing."""
@@ -140,7 +141,7 @@ class BucketedAllReducer:
             for p in self._params:
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
         if opt is not None:
-            opt._buckets = None  # re-materialize against the new flats
+            opt.drop_buckets()  # re-materialize against the new flats
             if opt_sd is not None:
                 opt.load_state_dict(opt_sd)
         for cb in getattr(self, "_on_rebuild", ()):

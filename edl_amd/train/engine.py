@@ -331,12 +331,10 @@ class TrainerEngine:
         if not (dist.is_initialized() and dist.get_world_size() > 1):
             return
         if hasattr(self.opt, "state_buffers"):
-            # FusedAdam: m, v and the step counter; FusedLARS: velocities
+            # FusedSGD: momentum; FusedAdam: m, v and the step counter;
+            # FusedLARS: velocities
             for t in self.opt.state_buffers():
                 dist.broadcast(t, src=src)
-        elif hasattr(self.opt, "_materialize"):
-            for bk in self.opt._materialize():
-                dist.broadcast(bk["m"], src=src)
 
     def _init_bf16_mirrors(self):
         """Per-bucket bf16 mirror of the flat fp32 params: each conv's

@@ -21,12 +21,18 @@ def _require_gpu():
     assert ops.available(), "edl_amd._C missing on a GPU box"
 
 
-def test_fused_sgd_matches_reference():
+# 1, 3: only the scalar tail; 4: one float4; 5: float4 + tail; 1027: more
+# than one block's worth of float4s plus a tail; the last: grid-stride
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 1027, 1 << 20 | 3])
+def test_fused_sgd_matches_reference(n):
     torch.manual_seed(0)
-    n = 1 << 20 | 3  # odd tail exercises the scalar path
-    p = torch.randn(n, device="cuda")
-    g = torch.randn(n, device="cuda")
-    m = torch.randn(n, device="cuda")
+    guard = 8  # elements on both sides; keeps p, g, m 16-byte aligned
+    bufs = [torch.full((guard + (n + 3) // 4 * 4 + guard,), s, device="cuda")
+            for s in (7.0, 5.0, 3.0)]
+    p, g, m = (b[guard:guard + n] for b in bufs)
+    for t in (p, g, m):
+        assert t.data_ptr() % 16 == 0
+        t.copy_(torch.randn(n, device="cuda"))
     pr, gr, mr = p.clone(), g.clone(), m.clone()
     lr, mu, wd, scale = 0.1, 0.9, 1e-4, 0.125
 
@@ -38,6 +44,23 @@ def test_fused_sgd_matches_reference():
     torch.cuda.synchronize()
     assert torch.allclose(m, mref, atol=1e-6), (m - mref).abs().max().item()
     assert torch.allclose(p, pref, atol=1e-6), (p - pref).abs().max().item()
+    # the guard elements around p and m (and g) come back bit-identical
+    for b, sentinel in zip(bufs, (7.0, 5.0, 3.0)):
+        for side in (b[:guard], b[guard + n:]):
+            assert side.numel() >= guard
+            assert torch.equal(side, torch.full_like(side, sentinel))
+
+
+def test_fused_sgd_rejects_bad_buffers():
+    ext = ops.ext()
+    p, g, m = (torch.zeros(16, device="cuda") for _ in range(3))
+    with pytest.raises(RuntimeError, match="16-byte"):
+        ext.fused_sgd(torch.zeros(17, device="cuda")[1:], g, m,
+                      0.1, 0.9, 1e-4, 1.0)
+    with pytest.raises(RuntimeError, match="size mismatch"):
+        ext.fused_sgd(p, g[:8], m, 0.1, 0.9, 1e-4, 1.0)
+    torch.cuda.synchronize()
+    assert torch.equal(p, torch.zeros_like(p))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
