@@ -255,4 +255,25 @@ void launch_dgc_compact(float* v, float* u, long long n, int* payload,
 void launch_dgc_scatter_add(float* out, long long n, const int* payload,
                             long long k, hipStream_t stream);
 
+// ---- image_prep.hip ---- (crop + bilinear resize + mirror + normalize of B
+// decoded uint8 RGB images into one channels-last batch [B, S, S, 3])
+// packed: the sources (HWC, 3 bytes per pixel, rows dense) back to back at
+// any byte offsets, nbytes in all (3 <= nbytes < 2^31). table: one row of
+// kImagePrepFields int32 per image, 16-byte aligned:
+//   [0] byte offset of the source in packed   [1] H   [2] W   [3] flip (0/1)
+//   [4..7] the fp32 BITS of x0, y0, cw, ch: the source window in pixel
+//          units, fractional allowed, cw, ch > 0
+// The kernel clamps every tap into the image and every byte index into
+// packed, whatever the table holds; the caller still checks the host copy
+// (ops/image_prep.py). k3 = 1/(255*std), b3 = mean/std: host fp32[3], read
+// before the launcher returns.
+constexpr int kImagePrepFields = 8;
+constexpr int kImagePrepRun = 4;   // consecutive output pixels per thread
+constexpr int kImagePrepRows = 4;  // output rows a thread walks
+int image_prep_blocks_per_image(int S);
+void launch_image_prep(const unsigned char* packed, long long nbytes,
+                       const int* table, void* out, int B, int S,
+                       int out_bf16, const float* k3, const float* b3,
+                       hipStream_t stream);
+
 }  // extern "C"

@@ -1493,9 +1493,74 @@ torch::Tensor gemm_tn3x3_small(torch::Tensor dy2d, torch::Tensor x,
   return c;
 }
 
+// ---- image input stage (image_prep.hip) -----------------------------------
+
+// packed: flat uint8 sources; table: int32 [B, kImagePrepFields] (layout in
+// launchers.h) -> channels-last [B, 3, S, S] bf16 or fp32, into `out` when
+// given. The table's CONTENT is checked on its host copy by the caller
+// (ops/image_prep.py); the kernel clamps every index regardless.
+torch::Tensor crop_resize_normalize(torch::Tensor packed, torch::Tensor table,
+                                    int64_t out_size, std::vector<double> mean,
+                                    std::vector<double> stdv, bool out_bf16,
+                                    c10::optional<torch::Tensor> out) {
+  const char* who = "crop_resize_normalize";
+  TORCH_CHECK(packed.is_cuda() && table.is_cuda() &&
+                  packed.device() == table.device(),
+              who, ": packed and table must sit on one GPU");
+  TORCH_CHECK(packed.scalar_type() == torch::kUInt8 && packed.dim() == 1 &&
+                  packed.is_contiguous(),
+              who, ": packed must be a flat contiguous uint8 tensor");
+  TORCH_CHECK(packed.numel() >= 3 && packed.numel() < (1LL << 31), who,
+              ": 3 <= packed.numel() < 2^31");
+  TORCH_CHECK(table.scalar_type() == torch::kInt32 && table.dim() == 2 &&
+                  table.size(1) == kImagePrepFields && table.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(table.data_ptr()) % 16 == 0,
+              who, ": table must be a contiguous, 16-byte aligned int32 [B, ",
+              kImagePrepFields, "] tensor");
+  const int64_t B = table.size(0), S = out_size;
+  TORCH_CHECK(B >= 1, who, ": B >= 1");
+  TORCH_CHECK(S >= 1 && S <= 16384, who, ": 1 <= out_size <= 16384");
+  TORCH_CHECK(B * image_prep_blocks_per_image((int)S) < (1LL << 31), who,
+              ": batch too large for one launch");
+  TORCH_CHECK(mean.size() == 3 && stdv.size() == 3, who,
+              ": mean and std have 3 entries");
+  float k3[3], b3[3];
+  for (int c = 0; c < 3; ++c) {
+    TORCH_CHECK(stdv[c] > 0.0, who, ": std > 0");
+    k3[c] = (float)(1.0 / (255.0 * stdv[c]));
+    b3[c] = (float)(mean[c] / stdv[c]);
+  }
+  const auto dtype = out_bf16 ? torch::kBFloat16 : torch::kFloat32;
+  torch::Tensor y;
+  if (out.has_value()) {
+    y = *out;
+    TORCH_CHECK(y.is_cuda() && y.device() == packed.device() &&
+                    y.scalar_type() == dtype && y.dim() == 4 &&
+                    y.size(0) == B && y.size(1) == 3 && y.size(2) == S &&
+                    y.size(3) == S && y.permute({0, 2, 3, 1}).is_contiguous(),
+                who, ": out must be a channels-last [B, 3, S, S] tensor of "
+                     "the output dtype on packed's device");
+  } else {
+    y = torch::empty({B, 3, S, S}, packed.options().dtype(dtype).memory_format(
+                                       torch::MemoryFormat::ChannelsLast));
+  }
+  launch_image_prep(packed.data_ptr<uint8_t>(), (long long)packed.numel(),
+                    table.data_ptr<int>(), y.data_ptr(), (int)B, (int)S,
+                    out_bf16 ? 1 : 0, k3, b3, cur_stream());
+  return y;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("crop_resize_normalize", &crop_resize_normalize,
+        "crop + bilinear resize + mirror + mean/std normalize of packed uint8 "
+        "RGB sources -> channels-last [B, 3, S, S] (table: int32 [B, 8] = "
+        "{offset, H, W, flip, bits of x0, y0, cw, ch})",
+        py::arg("packed"), py::arg("table"), py::arg("out_size"),
+        py::arg("mean"), py::arg("std"), py::arg("out_bf16"),
+        py::arg("out") = py::none());
+  m.attr("IMAGE_PREP_FIELDS") = kImagePrepFields;
   m.def("fused_sgd", &fused_sgd,
         "fused flat momentum-SGD update (p,g,m flat fp32; folds grad_scale)",
         py::arg("p"), py::arg("g"), py::arg("m"), py::arg("lr"),

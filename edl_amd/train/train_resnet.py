@@ -2,7 +2,8 @@
 
 Spawned by the edlrun launcher (one process per GPU); reads the env
 contract (TrainerEnv), builds the RCCL world, trains ResNet50_vd (or any
-model in the zoo) on synthetic ImageNet-shaped data with elastic
+model in the zoo) on synthetic ImageNet-shaped data, or on image files
+(--image_root with --train_list or --data_dir: data/images.py), with elastic
 stop-resume: per-epoch (and optional per-N-steps) checkpoints, LR rescaled
 by the linear-scaling rule on every world change, train status reported to
 the coordination store so the generator can veto near-end scaling.
@@ -44,7 +45,8 @@ def parse_args(argv=None):
                    help="txt record files: train through the elastic "
                         "data plane (leader-balanced Reader) instead of "
                         "the synthetic loader; records deterministically "
-                        "seed synthetic images (no dataset network)")
+                        "seed synthetic images, or with --image_root name "
+                        "the image files to decode")
     p.add_argument("--image_hw", type=int, default=224)
     p.add_argument("--use_hip_ops", type=int, default=1)
     p.add_argument("--graph_capture", type=int, default=None)
@@ -91,7 +93,34 @@ def parse_args(argv=None):
     p.add_argument("--skip_nonfinite", type=int, default=0,
                    help="skip the update of a step whose gradient norm is "
                         "inf/nan")
+    # image files (reference train_with_fleet.py --data_dir + dali.py /
+    # utils/reader.py): `relpath label` records decoded from --image_root
+    p.add_argument("--image_root", default=None,
+                   help="directory the records' image paths are relative "
+                        "to: with --data_dir the data-plane records are "
+                        "decoded from it, else --train_list names them")
+    p.add_argument("--train_list", default=None,
+                   help="file of `relpath label` lines (with --image_root, "
+                        "without --data_dir), sharded records[rank::world]")
+    p.add_argument("--val_list", default=None,
+                   help="file of `relpath label` lines for --eval_steps")
+    p.add_argument("--lower_scale", type=float, default=0.08)
+    p.add_argument("--lower_ratio", type=float, default=3.0 / 4.0)
+    p.add_argument("--upper_ratio", type=float, default=4.0 / 3.0)
+    p.add_argument("--resize_short", type=float, default=None,
+                   help="eval: short side before the centre crop "
+                        "(default image_hw * 256/224)")
+    p.add_argument("--input_dtype", default="auto",
+                   choices=["auto", "fp32", "bf16"],
+                   help="dtype of the image batches from --image_root; auto "
+                        "= bf16 when the engine runs bf16 on a GPU")
+    p.add_argument("--decode_workers", type=int, default=8)
     return p.parse_args(argv)
+
+
+def read_list(path):
+    with open(path) as f:
+        return [ln.strip() for ln in f if ln.strip()]
 
 
 def main(argv=None):
@@ -148,34 +177,56 @@ def main(argv=None):
     report(TrainStatus.RUNNING)
     shape = (3, args.image_hw, args.image_hw)
     cl = engine.channels_last and engine.device.type == "cuda"
+    if (args.train_list or args.val_list) and not args.image_root:
+        raise SystemExit("--train_list / --val_list need --image_root")
+    if args.image_root and not (args.data_dir or args.train_list):
+        raise SystemExit("--image_root needs --data_dir or --train_list")
+    if args.train_list and args.data_dir:
+        raise SystemExit("--train_list and --data_dir exclude each other")
+
+    def image_loader(records, train, epoch=0):
+        from ..data.images import ImageRecordLoader
+
+        bf16 = (args.input_dtype == "bf16" or
+                (args.input_dtype == "auto" and engine.device.type == "cuda"
+                 and engine.dtype == torch.bfloat16))
+        return ImageRecordLoader(
+            records, args.image_root, args.batch_size, engine.device,
+            out_size=args.image_hw, train=train, seed=1234, epoch=epoch,
+            out_dtype=torch.bfloat16 if bf16 else torch.float32,
+            num_workers=args.decode_workers, lower_scale=args.lower_scale,
+            lower_ratio=args.lower_ratio, upper_ratio=args.upper_ratio,
+            resize_short=args.resize_short)
+
+    train_records = None
+    if args.train_list:
+        rank, world = engine.env.global_rank, engine.world_size
+        train_records = read_list(args.train_list)[rank::world]
     loader = None
-    if not args.data_dir:
+    if not args.data_dir and train_records is None:
         loader = SyntheticImageNet(
             args.batch_size, engine.device, image_shape=shape,
             channels_last=cl, seed=1234 + engine.env.global_rank,
         )
 
     eval_loader = None
-    if args.eval_steps > 0:
+    if args.eval_steps > 0 and args.val_list:
+        rank, world = engine.env.global_rank, engine.world_size
+        eval_loader = image_loader(read_list(args.val_list)[rank::world],
+                                   train=False)
+    elif args.eval_steps > 0:
         # held-out synthetic batches: a seed of their own
         eval_loader = SyntheticImageNet(
             args.batch_size, engine.device, image_shape=shape,
             channels_last=cl, seed=987654 + engine.env.global_rank,
         )
 
-    def plane_epoch_loader():
-        """Elastic data plane: leader-balanced record slices -> loader.
-        Ranks can receive slightly unequal record counts, so all ranks
+    def agree_steps(steps):
+        """Ranks can hold slightly unequal record counts, so all ranks
         agree on the MIN step count before training (collectives must
         stay matched across the world)."""
         import torch.distributed as dist
 
-        from ..data.plane import RecordImageSet, fetch_epoch_records
-
-        recs = fetch_epoch_records(tenv, args.data_dir, args.batch_size)
-        ds = RecordImageSet(recs, args.batch_size, engine.device,
-                            image_shape=shape, channels_last=cl)
-        steps = ds.steps()
         if dist.is_initialized():
             t = torch.tensor([steps], dtype=torch.long,
                              device=engine.device
@@ -184,7 +235,21 @@ def main(argv=None):
             steps = int(t.item())
         if args.steps_per_epoch:
             steps = min(steps, args.steps_per_epoch)
-        return ds, steps
+        return steps
+
+    def plane_epoch_loader(epoch):
+        """Elastic data plane: leader-balanced record slices -> loader."""
+        from ..data.plane import RecordImageSet, fetch_epoch_records
+
+        recs = fetch_epoch_records(tenv, args.data_dir, args.batch_size)
+        if args.image_root:
+            # no full batch: report 0 steps (below) rather than build a loader
+            ds = (image_loader(recs, True, epoch)
+                  if len(recs) >= args.batch_size else None)
+        else:
+            ds = RecordImageSet(recs, args.batch_size, engine.device,
+                                image_shape=shape, channels_last=cl)
+        return ds, agree_steps(ds.steps() if ds is not None else 0)
 
     def on_step(epoch, it):
         if args.checkpoint_steps and (engine.global_step % args.checkpoint_steps == 0):
@@ -196,10 +261,13 @@ def main(argv=None):
         if epoch == args.num_epochs - 1:
             report(TrainStatus.NEARTHEEND)
         if args.data_dir:
-            ep_loader, ep_steps = plane_epoch_loader()
+            ep_loader, ep_steps = plane_epoch_loader(epoch)
             if ep_steps == 0:
                 log.warning("epoch %d: no full batch from the data plane", epoch)
                 continue
+        elif train_records is not None:
+            ep_loader = image_loader(train_records, True, epoch)
+            ep_steps = agree_steps(ep_loader.steps())
         else:
             ep_loader, ep_steps = loader, args.steps_per_epoch
         if args.use_mixup:
