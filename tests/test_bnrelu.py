@@ -275,18 +275,26 @@ class TestConvFusedStats:
 
     @pytest.mark.parametrize("shape", [
         (2, 64, 64, 14, 1),    # 1x1 (gemm_bt epilogue)
-        (2, 64, 128, 14, 3),   # 3x3 (conv3x3 epilogue)
+        # 3x3, M = 392 = 4 tiles: conv3x3_pick_splitk takes split-K (2
+        # slices), the binding returns no partials and BOTH modules compute
+        # BN's own stats — the fallback, not the epilogue
+        (2, 64, 128, 14, 3),
         (2, 3, 32, 16, 3),     # stem (small kernel epilogue)
+        # 3x3, M = 12482 = 196 tiles: the non-split conv3x3 epilogue, stats
+        # stored uncapped into [98, 512]
+        (2, 64, 256, 79, 3),
     ])
     def test_conv_epilogue_stats_match_bn_stats(self, shape, monkeypatch):
         """BN fed conv-folded stats partials must match BN computing its
         own stats on the same bf16 output (train mode, running stats and
-        y compared)."""
+        y compared). For the dense 3x3 shapes a spy on the stats bindings
+        asserts whether the fused run really received partials."""
         self._gpu()
         import copy
 
         import edl_amd.ops.conv as conv_mod
         from edl_amd.models.resnet_vd import ConvBN
+        from edl_amd.ops import ext
 
         n, ci, co, hw, k = shape
         torch.manual_seed(31)
@@ -296,8 +304,19 @@ class TestConvFusedStats:
         x = torch.randn(n, ci, hw, hw, device="cuda").to(torch.bfloat16)
         x = x.contiguous(memory_format=torch.channels_last)
 
+        got_part = []
+        if k == 3 and ci % 64 == 0:
+            for name in ("conv3x3_fwd_stats", "conv3x3_fwd_stats_padded"):
+                def spy(*args, _real=getattr(ext(), name)):
+                    res = _real(*args)
+                    got_part.append(res[1] is not None)
+                    return res
+                monkeypatch.setattr(ext(), name, spy)
+
         monkeypatch.setattr(conv_mod, "_BN_STATS_FUSED", True)
         y1 = m1(x)
+        if k == 3 and ci % 64 == 0:
+            assert got_part == [shape == (2, 64, 256, 79, 3)], got_part
         monkeypatch.setattr(conv_mod, "_BN_STATS_FUSED", False)
         y2 = m2(x)
         assert torch.allclose(y1.float(), y2.float(), atol=1e-2, rtol=1e-2), \
