@@ -19,6 +19,10 @@
 //     -> conflict-free ds_read_b128 fragments
 //   * row-clamped A loads for the M tail (C-write is row-guarded)
 //   * two tile shapes: 128x128 (N % 128 == 0) and 256x64
+//   * RADD epilogue (launch_gemm_bt_add): C = bf16(float(bf16(acc)) + R), the
+//     residual-gradient add of the 1x1 dgrad folded in; R reaches the lanes
+//     through the staging buffer that is dead in the last K-tile (RADD 1) or
+//     by plain 2-byte global loads (RADD 2, the measured alternative)
 #include "common.h"
 #include "launchers.h"
 
@@ -29,7 +33,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool SPLITK = false,
-          bool V2 = false>
+          bool V2 = false, int RADD = 0>
 __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     void* __restrict__ C_any, const int M, const int N, const int K,
@@ -40,6 +44,11 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   // SPLITK: grid.y k-slices; each block atomically folds its fp32 partial
   // tile into C (fp32, pre-zeroed). Wgrad-shaped GEMMs (tiny [Cout, Cin]
   // output, K = M ~ 1e5) otherwise serialize on 1-2 blocks.
+  // RADD: the bn_part slot carries R, a bf16 [M, N] addend laid out like C
+  // (no stats with it, so the existing kernels keep their argument list):
+  // C = bf16(float(bf16(acc)) + float(R)) — the accumulator is rounded to
+  // bf16 FIRST, which is bit-for-bit gemm_bt followed by a bf16 add.
+  static_assert(RADD == 0 || (!SPLITK && !V2), "RADD: plain bf16 loop only");
   bf16* C = SPLITK ? nullptr : (bf16*)C_any;
   float* Cf = SPLITK ? (float*)C_any : nullptr;
   constexpr int BK = 64;
@@ -146,6 +155,29 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     }
   };
 
+  // RADD 1: each wave stages ITS 64x64 sub-tile of R (8 KiB, 8 glds) into
+  // its own slice of staging buffer `buf`; it alone reads that slice back.
+  // LDS image: row r at r*128, 16-B slot s holds global slot s ^ f(r) with
+  // f(r) = ((r >> 2) & 3) << 1 — the four rows (lane>>4)*4 + reg that one
+  // epilogue ds_read_u16 touches then sit in four different 32-B bank
+  // groups (row stride 128 B alone would put them 2-way on the 64 banks).
+  // Rows past M are clamped like A's: read in bounds, never stored.
+  auto stage_r = [&](int buf) {
+    const bf16* R = (const bf16*)bn_part;
+    char* rbase = lds + buf * (A_BYTES + B_BYTES) + wave * 8192;
+#pragma unroll
+    for (int ch = 0; ch < 8; ++ch) {
+      const int r = ch * 8 + (lane >> 3);
+      const int gslot = (lane & 7) ^ (((r >> 2) & 3) << 1);
+      long long grow = m0 + wm + r;
+      if (grow >= M) grow = M - 1;
+      const bf16* src = R + grow * N + n0 + wn + gslot * 8;
+      __builtin_amdgcn_global_load_lds(
+          (const __attribute__((address_space(1))) void*)src,
+          (__attribute__((address_space(3))) void*)(rbase + ch * 1024), 16, 0, 0);
+    }
+  };
+
   int kt_begin = 0, kt_end = K / BK;
   if (SPLITK) {
     const int per = (kt_end + gridDim.y - 1) / gridDim.y;
@@ -154,6 +186,11 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     if (kt_begin >= kt_end) return;
   }
   stage(0, kt_begin);
+  // buffer (K/BK)&1 never receives another A/B tile once the last K-tile
+  // is being computed; with ONE K-tile it is free from the start and R
+  // rides along with the first stage
+  if constexpr (RADD == 1)
+    if (kt_end == 1) stage_r(1);
   __syncthreads();
 
   // v2 main loop: 4 phases per K-tile — each phase prefetches a quarter of
@@ -191,6 +228,11 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int cur = (kt - kt_begin) & 1;
     if (kt + 1 < kt_end) stage(cur ^ 1, kt + 1);
+    else if constexpr (RADD == 1) {
+      // last tile: R lands under its MFMAs; the closing __syncthreads
+      // (vmcnt(0) + barrier) retires it before the epilogue reads
+      if (kt_end > 1) stage_r(cur ^ 1);
+    }
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       bf16x8 a[4], b[4];
@@ -212,6 +254,38 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   // row=(lane>>4)*4+reg ----
   const int cn = lane & 15;
   const int r4 = (lane >> 4) * 4;
+  if constexpr (RADD != 0) {
+    const bf16* R = (const bf16*)bn_part;
+    const char* rbase =
+        lds + ((K / BK) & 1) * (A_BYTES + B_BYTES) + wave * 8192;
+#pragma unroll
+    for (int mf = 0; mf < 4; ++mf) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int r = mf * 16 + r4 + reg;
+        const int m = m0 + wm + r;
+        if (m < M) {
+          const long long off = (long long)m * N + n0 + wn + cn;
+#pragma unroll
+          for (int nf = 0; nf < 4; ++nf) {
+            bf16 rv;
+            if constexpr (RADD == 1) {
+              const int c = nf * 16 + cn;
+              rv = *(const bf16*)(rbase + r * 128 +
+                                  (((c >> 3) ^ (((r >> 2) & 3) << 1)) << 4) +
+                                  (c & 7) * 2);
+            } else {
+              rv = R[off + nf * 16];
+            }
+            const bf16 yb = __float2bfloat16(acc[mf][nf][reg]);
+            C[off + nf * 16] = __float2bfloat16(__bfloat162float(yb) +
+                                                __bfloat162float(rv));
+          }
+        }
+      }
+    }
+    return;
+  }
   float ls[4] = {0, 0, 0, 0}, lq[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int mf = 0; mf < 4; ++mf) {
@@ -374,6 +448,50 @@ extern "C" void launch_gemm_bt(const void* A, const void* B, void* C, int M,
       hipLaunchKernelGGL((gemm_bt_kernel<BM, BN, 4, 1>), dim3(grid), dim3(256),
                          lds_bytes, s, (const bf16*)A, (const bf16*)B, C, M, N,
                          K, bn_part, use_store_lds());
+  }
+}
+
+static int use_add_global() {
+  // EDL_BT_ADD_R=global: read R with plain 2-byte global loads in the C/D
+  // fragment map instead of staging it through the dead LDS buffer. Kept
+  // for A/B (tools/gemm_bench.py --dgrad-add; figures in docs/kernels.md).
+  static const int v = []() {
+    const char* e = getenv("EDL_BT_ADD_R");
+    return e != nullptr && e[0] == 'g';
+  }();
+  return v;
+}
+
+// C = bf16(float(bf16(A @ B^T)) + float(R)); R bf16 [M, N] laid out like C
+extern "C" void launch_gemm_bt_add(const void* A, const void* B, const void* R,
+                                   void* C, int M, int N, int K,
+                                   hipStream_t s) {
+  // R travels in the bn_part slot (never dereferenced as float)
+  float* r = (float*)const_cast<void*>(R);
+  if (N % 128 == 0) {
+    constexpr int BM = 128, BN = 128;
+    const int grid = ((M + BM - 1) / BM) * (N / BN);
+    const int lds_bytes = 2 * (BM * 64 * 2 + BN * 64 * 2);
+    if (use_add_global())
+      hipLaunchKernelGGL((gemm_bt_kernel<BM, BN, 2, 2, false, false, 2>),
+                         dim3(grid), dim3(256), lds_bytes, s, (const bf16*)A,
+                         (const bf16*)B, C, M, N, K, r, 0);
+    else
+      hipLaunchKernelGGL((gemm_bt_kernel<BM, BN, 2, 2, false, false, 1>),
+                         dim3(grid), dim3(256), lds_bytes, s, (const bf16*)A,
+                         (const bf16*)B, C, M, N, K, r, 0);
+  } else {  // N % 64 == 0
+    constexpr int BM = 256, BN = 64;
+    const int grid = ((M + BM - 1) / BM) * (N / BN);
+    const int lds_bytes = 2 * (BM * 64 * 2 + BN * 64 * 2);
+    if (use_add_global())
+      hipLaunchKernelGGL((gemm_bt_kernel<BM, BN, 4, 1, false, false, 2>),
+                         dim3(grid), dim3(256), lds_bytes, s, (const bf16*)A,
+                         (const bf16*)B, C, M, N, K, r, 0);
+    else
+      hipLaunchKernelGGL((gemm_bt_kernel<BM, BN, 4, 1, false, false, 1>),
+                         dim3(grid), dim3(256), lds_bytes, s, (const bf16*)A,
+                         (const bf16*)B, C, M, N, K, r, 0);
   }
 }
 

@@ -172,6 +172,9 @@ void launch_bn_bwd_fused(const void* dy, const unsigned char* mask,
 int gemm_bt_tiles_m(int M, int N);
 void launch_gemm_bt(const void* A, const void* B, void* C, int M, int N,
                     int K, float* bn_part, hipStream_t s);
+// C = bf16(float(bf16(A @ B^T)) + float(R)), R bf16 [M, N] laid out like C
+void launch_gemm_bt_add(const void* A, const void* B, const void* R, void* C,
+                        int M, int N, int K, hipStream_t s);
 void launch_gemm_bt_splitk(const void* A, const void* B, float* Cf32, int M,
                            int N, int K, int splitk, hipStream_t s);
 

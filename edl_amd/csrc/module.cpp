@@ -1013,6 +1013,28 @@ std::vector<torch::Tensor> gemm_bt_stats(torch::Tensor a, torch::Tensor b) {
   return gemm_bt_impl(a, b, true);
 }
 
+// C = bf16(float(bf16(A @ B^T)) + float(R)): gemm_bt followed by a bf16 add,
+// bit for bit, in one kernel (the 1x1 dgrad + residual-gradient sum). r is
+// read in place and never written; no stats epilogue with it.
+torch::Tensor gemm_bt_add(torch::Tensor a, torch::Tensor b, torch::Tensor r) {
+  check_bt_operands(a, b, "gemm_bt_add");
+  const int M = (int)a.size(0), K = (int)a.size(1), N = (int)b.size(0);
+  TORCH_CHECK(r.scalar_type() == torch::kBFloat16, "gemm_bt_add: r bf16 only");
+  TORCH_CHECK(r.is_cuda() && r.device() == a.device(),
+              "gemm_bt_add: r on another device than a");
+  TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == N,
+              "gemm_bt_add: r shape [M, N] required");
+  TORCH_CHECK(r.is_contiguous(), "gemm_bt_add: r not contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(r.data_ptr()) % 16 == 0,
+              "gemm_bt_add: r base not 16-byte aligned");
+  auto ac = a.contiguous();
+  auto bc = b.contiguous();
+  auto c = torch::empty({M, N}, a.options());
+  launch_gemm_bt_add(ac.data_ptr(), bc.data_ptr(), r.data_ptr(), c.data_ptr(),
+                     M, N, K, cur_stream());
+  return c;
+}
+
 // flat zero-halo padded copy of x [N, C, H, W] channels_last bf16, widened
 // to cpad >= C channels: N * (H+2) * (W+2) * cpad elements
 torch::Tensor pad_nhwc_flat(const torch::Tensor& x, int cpad, hipStream_t s) {
@@ -1686,6 +1708,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "conv3x3_fwd + BN stats partials -> (y2d, part-or-None)");
   m.def("gemm_bt_stats", &gemm_bt_stats,
         "gemm_bt + BN stats partials -> (C, part)");
+  m.def("gemm_bt_add", &gemm_bt_add,
+        "gemm_bt with a bf16 [M,N] addend: bf16(float(bf16(A@B^T)) + R)",
+        py::arg("a"), py::arg("b"), py::arg("r"));
   m.def("transpose_pad", &transpose_pad,
         "bf16 [M,C] -> [C, ceil64(M)] transpose with zero pad");
   m.def("gemm_bt_splitk", &gemm_bt_splitk,

@@ -25,15 +25,24 @@ class ConvBN(nn.Module):
                               bias=False)
         self.bn = BNReLU2d(cout, act=act)
 
-    def forward(self, x, pad_out=False):
+    def forward(self, x, pad_out=False, fork=False):
+        # fork: x has a second consumer; returns (y, x_fork) and the caller
+        # feeds x_fork to it, so a 1x1 conv's dgrad receives both of x's
+        # gradients and sums them in its epilogue (Conv2dFast.forward)
         # conv folds BN stats partials into its epilogue when training.
         # The conv output feeds only this BN, so a 3x3 conv may take its
         # dy from the BN backward in the padded layout (dx_pad).
         # pad_out: the caller feeds the result to exactly one 3x3
         # Conv2dFast — the BN writes that conv's padded input layout.
-        y = self.conv(x, bn_stats=self.bn.training, dx_pad=True)
-        return self.bn(y, partials=self.conv.pop_bn_part(), pad_out=pad_out,
-                       dx_pad=self.conv.pop_dy_pad())
+        x_fork = None
+        if fork:
+            y, x_fork = self.conv(x, bn_stats=self.bn.training, dx_pad=True,
+                                  fork=True)
+        else:
+            y = self.conv(x, bn_stats=self.bn.training, dx_pad=True)
+        y = self.bn(y, partials=self.conv.pop_bn_part(), pad_out=pad_out,
+                    dx_pad=self.conv.pop_dy_pad())
+        return (y, x_fork) if fork else y
 
 
 class VdShortcut(nn.Module):
@@ -73,9 +82,13 @@ class BottleneckVd(nn.Module):
         self.shortcut = VdShortcut(cin, cout, stride, if_first)
 
     def forward(self, x):
-        s = self.shortcut(x)
+        # x feeds conv0 and the shortcut: conv0 forks it, and its dgrad adds
+        # the shortcut's gradient in the GEMM epilogue (x_fork is x itself
+        # wherever that route does not apply).
         # conv0's output has one consumer, conv1's 3x3
-        y0 = self.conv0(x, pad_out=self.conv1.conv.takes_padded())
+        y0, x_fork = self.conv0(x, pad_out=self.conv1.conv.takes_padded(),
+                                fork=True)
+        s = self.shortcut(x_fork)
         y = self.conv2(self.conv1(y0), bn_stats=self.bn_add.training)
         return self.bn_add(y, s, partials=self.conv2.pop_bn_part())
 

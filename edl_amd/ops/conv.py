@@ -32,6 +32,21 @@ _WGRAD = os.environ.get("EDL_WGRAD", "tn")
 # per-row div/mod gather addressing amortizes worse at small M. Route by
 # Cin; override with EDL_WGRAD3_TN_MAXC (0 = never, 9999 = always).
 _WGRAD3_MAXC = int(os.environ.get("EDL_WGRAD3_TN_MAXC", "128"))
+# A 1x1 conv whose input has a second consumer (the bottleneck's shortcut)
+# can hand that consumer a pass-through of the input ("fork"); backward then
+# receives both gradients and the dgrad GEMM adds the second one in its
+# epilogue (gemm_bt_add) instead of autograd summing them with an
+# elementwise kernel. 0 = autograd sums, as before.
+_DGRAD_ADD = os.environ.get("EDL_DGRAD_ADD", "1") == "1"
+
+
+def _fusable_addend(t, m, c):
+    """True iff gradient t can ride in the dgrad epilogue as it stands: bf16
+    [m, c] rows, dense, 16-byte aligned. Anything else (an expanded or
+    strided tensor, another dtype) is added by torch after the GEMM."""
+    return (t.dtype == torch.bfloat16 and t.is_cuda
+            and tuple(t.shape) == (m, c) and t.is_contiguous()
+            and t.data_ptr() % 16 == 0)
 
 
 class _Conv1x1Hip(torch.autograd.Function):
@@ -42,29 +57,45 @@ class _Conv1x1Hip(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2d, w_param, w_bf16, wt_cached, grad_tgt,
-                part_out=None):
+                part_out=None, fork=False):
         # w_param: the fp32 (or bf16) parameter view — the DIFFERENTIABLE
         # input; w_bf16/wt_cached: per-step cached compute copies. Grads
         # come back in fp32 straight from the split-K kernel: no cast
         # nodes on the weight path at all. grad_tgt (direct-grad mode,
         # world 1): the weight's bucket-view .grad — backward accumulates
         # into it in-kernel and returns None, skipping AccumulateGrad.
+        # fork: also return x2d itself as a second output. The caller gives
+        # it to x's OTHER consumer, so both of x's gradients arrive in this
+        # backward and the dgrad GEMM sums them in its epilogue.
         ctx.save_for_backward(x2d)
         ctx.wt = wt_cached  # [Cin, Cout] bf16, derived per weight epoch
         ctx.w_dtype = w_param.dtype
         ctx.grad_tgt = grad_tgt
+        ctx.set_materialize_grads(False)  # an unused output gives None
         if part_out is not None:
             y2d, part = ext().gemm_bt_stats(x2d, w_bf16)
             part_out.append(part)
-            return y2d
-        return ext().gemm_bt(x2d, w_bf16)
+        else:
+            y2d = ext().gemm_bt(x2d, w_bf16)
+        if fork:
+            return y2d, x2d
+        return y2d
 
     @staticmethod
-    def backward(ctx, dy2d):
+    def backward(ctx, dy2d, dfork=None):
         (x2d,) = ctx.saved_tensors
+        none6 = (None,) * 6
+        if dy2d is None:  # only the fork was used
+            return (dfork,) + none6
         dy2d = dy2d.contiguous()
         e = ext()
-        dx = e.gemm_bt(dy2d, ctx.wt)
+        # dfork and dy2d are only ever read
+        if dfork is None:
+            dx = e.gemm_bt(dy2d, ctx.wt)
+        elif _fusable_addend(dfork, dy2d.shape[0], ctx.wt.shape[0]):
+            dx = e.gemm_bt_add(dy2d, ctx.wt, dfork)
+        else:
+            dx = torch.add(e.gemm_bt(dy2d, ctx.wt), dfork)
         # wgrad: TN with reduction over huge M. Default: the direct TN
         # split-K kernel reading dY/X in their native [M, C] layout (the
         # "transpose" happens in the LDS fragment reads — gemm_tn.hip).
@@ -78,13 +109,13 @@ class _Conv1x1Hip(torch.autograd.Function):
                 e.gemm_tn_splitk(
                     dy2d, x2d, 0,
                     ctx.grad_tgt.view(ctx.grad_tgt.shape[0], -1))
-                return dx, None, None, None, None, None
+                return (dx,) + none6
             dw = e.gemm_tn_splitk(dy2d, x2d, 0)
         else:
             dw = e.gemm_bt_splitk(e.transpose_pad(dy2d), e.transpose_pad(x2d), 0)
         if dw.dtype != ctx.w_dtype:
             dw = dw.to(ctx.w_dtype)
-        return dx, dw, None, None, None, None
+        return (dx, dw) + none6[1:]
 
 
 _CONV3X3 = os.environ.get("EDL_CONV3X3", "hip")
@@ -553,9 +584,27 @@ class Conv2dFast(nn.Conv2d):
             self.weight.detach().permute(1, 0, 2, 3).flip(2, 3),
             _small_cpt(self.out_channels))
 
-    def forward(self, x, bn_stats=False, dx_pad=False):
+    def _forks(self, x):
+        """True if forward(x, fork=True) hands out a pass-through of x from
+        the 1x1 autograd node: only the hip bf16 route with a gradient to
+        sum, on an input _forward_1x1 neither subsamples nor copies."""
+        return (_DGRAD_ADD and _CONV1X1 == "hip" and x.is_cuda and available()
+                and x.dtype == torch.bfloat16
+                and x.requires_grad and torch.is_grad_enabled()
+                and self.kernel_size == (1, 1) and self.stride == (1, 1)
+                and self.groups == 1 and self.padding == (0, 0)
+                and self.bias is None
+                and self.in_channels % 64 == 0 and self.out_channels % 64 == 0
+                and x.is_contiguous(memory_format=torch.channels_last))
+
+    def forward(self, x, bn_stats=False, dx_pad=False, fork=False):
         # dx_pad: the caller feeds the output to exactly one BN and will
         # hand it pop_dy_pad()
+        # fork: return (y, x_fork); the caller gives x_fork, not x, to x's
+        # other consumer (see _Conv1x1Hip). x_fork is x itself wherever
+        # the dgrad-add route does not apply.
+        if fork and not self._forks(x):
+            return self.forward(x, bn_stats, dx_pad), x
         self._bn_part = None
         self._dy_pad = None
         bn_stats = bn_stats and _BN_STATS_FUSED
@@ -581,7 +630,7 @@ class Conv2dFast(nn.Conv2d):
             and self.padding == (0, 0)
             and self.bias is None
         ):
-            return self._forward_1x1(x, bn_stats)
+            return self._forward_1x1(x, bn_stats, fork)
         return super().forward(x)
 
     def _forward_dense3x3(self, x, bn_stats, dx_pad):
@@ -671,7 +720,10 @@ class Conv2dFast(nn.Conv2d):
         n, _, h, w = x.shape
         return _nchw_view(y2d, n, *_out_hw(h, w, self.stride[0]))
 
-    def _forward_1x1(self, x, bn_stats):
+    def _forward_1x1(self, x, bn_stats, fork=False):
+        # fork (checked by forward: hip route, bf16, stride 1, x dense
+        # channels_last and requiring grad): returns (y, x_fork), x_fork a
+        # pass-through of x that comes out of the SAME autograd node as y
         n, c, h, w = x.shape
         sh, sw = self.stride
         if sh != 1 or sw != 1:
@@ -685,6 +737,7 @@ class Conv2dFast(nn.Conv2d):
         if not (_CONV1X1 == "hip" and available()
                 and x2d.dtype == torch.bfloat16
                 and c % 64 == 0 and co % 64 == 0):
+            assert not fork  # _forks() admits the hip route only
             return _nchw_view(x2d @ wt.t(), n, h, w)
         mb = getattr(self.weight, "_edl_bf16", None)
         if mb is not None:  # engine bucket mirror: free bf16 view
@@ -704,7 +757,13 @@ class Conv2dFast(nn.Conv2d):
         if grad_tgt is not None and not grad_tgt.is_contiguous():
             grad_tgt = None
         holder = [] if bn_stats else None
-        y2d = _Conv1x1Hip.apply(x2d, wt, w_bf16, wt_t, grad_tgt, holder)
+        if fork:
+            y2d, xf2d = _Conv1x1Hip.apply(x2d, wt, w_bf16, wt_t, grad_tgt,
+                                          holder, True)
+        else:
+            y2d = _Conv1x1Hip.apply(x2d, wt, w_bf16, wt_t, grad_tgt, holder)
         if holder:
             self._bn_part = holder[0]
+        if fork:
+            return _nchw_view(y2d, n, h, w), _nchw_view(xf2d, n, h, w)
         return _nchw_view(y2d, n, h, w)

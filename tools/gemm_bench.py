@@ -1,6 +1,7 @@
 """Microbench: gemm_bt vs torch.matmul (hipBLASLt) on the ResNet50_vd
 conv1x1 shapes at bs32. Run on a GPU box:
     python tools/gemm_bench.py
+    python tools/gemm_bench.py --dgrad-add   # fused residual-add dgrad
 """
 import os
 import sys
@@ -92,8 +93,78 @@ def main_wgrad3():
             t_bt / t_tn))
 
 
+# (M, N=Cin, K=Cout, blocks) of the 16 BottleneckVd conv0 dgrads at bs32
+DGRAD_ADD_SHAPES = [
+    (100352, 64, 64, 1), (100352, 256, 64, 2), (100352, 256, 128, 1),
+    (25088, 512, 128, 3), (25088, 512, 256, 1),
+    (6272, 1024, 256, 5), (6272, 1024, 512, 1),
+    (1568, 2048, 512, 2),
+]
+
+
+def main_dgrad_add(windows=9, l3_bytes=256 << 20):
+    """conv0 dgrad + residual-gradient add, per shape: (a) gemm_bt + torch
+    add, (b) gemm_bt_add, (c) gemm_bt alone. Operands rotate over enough
+    buffer sets to exceed the L3, as the training step sees them cold.
+    Median [min..max] us per call over `windows` event-timed replays of one
+    graph-captured pass over the sets. EDL_BT_ADD_R=global selects the other R-load
+    variant of (b): run once per variant."""
+    e = ops.ext()
+    print("R load: %s" % os.environ.get("EDL_BT_ADD_R", "lds"))
+    print("%-22s %3s %-24s %-24s %-24s" % (
+        "shape (M,N,K)", "x", "(a) bt + add", "(b) bt_add", "(c) bt alone"))
+    tot = {"a": 0.0, "b": 0.0, "c": 0.0}
+    for M, N, K, cnt in DGRAD_ADD_SHAPES:
+        set_bytes = 2 * (M * K + N * K + 2 * M * N)
+        nsets = max(2, -(-int(1.25 * l3_bytes) // set_bytes))
+        sets = [(torch.randn(M, K, device="cuda").to(torch.bfloat16),
+                 torch.randn(N, K, device="cuda").to(torch.bfloat16),
+                 torch.randn(M, N, device="cuda").to(torch.bfloat16))
+                for _ in range(nsets)]
+        fns = {
+            "a": lambda a, b, r: e.gemm_bt(a, b) + r,
+            "b": lambda a, b, r: e.gemm_bt_add(a, b, r),
+            "c": lambda a, b, r: e.gemm_bt(a, b),
+        }
+        cols = []
+        for key in ("a", "b", "c"):
+            fn = fns[key]
+            for a, b, r in sets:  # warm-up pass
+                fn(a, b, r)
+            torch.cuda.synchronize()
+            # one pass over the sets as a graph: the step runs captured,
+            # so host launch cost must not count against the two-kernel (a)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for a, b, r in sets:
+                    fn(a, b, r)
+            g.replay()
+            torch.cuda.synchronize()
+            us = []
+            for _ in range(windows):
+                t0 = torch.cuda.Event(enable_timing=True)
+                t1 = torch.cuda.Event(enable_timing=True)
+                t0.record()
+                g.replay()
+                t1.record()
+                torch.cuda.synchronize()
+                us.append(t0.elapsed_time(t1) * 1e3 / nsets)
+            del g
+            us.sort()
+            med = us[len(us) // 2]
+            tot[key] += med * cnt
+            cols.append("%7.1f [%6.1f..%6.1f]" % (med, us[0], us[-1]))
+        print("%-22s %3d %-24s %-24s %-24s" % (str((M, N, K)), cnt, *cols))
+        del sets
+        torch.cuda.empty_cache()
+    print("per step (x counts): (a) %.1f us  (b) %.1f us  (c) %.1f us" % (
+        tot["a"], tot["b"], tot["c"]))
+
+
 if __name__ == "__main__":
-    if "--wgrad" in sys.argv:
+    if "--dgrad-add" in sys.argv:
+        main_dgrad_add()
+    elif "--wgrad" in sys.argv:
         main_wgrad()
     elif "--wgrad3" in sys.argv:
         main_wgrad3()
