@@ -72,14 +72,23 @@ extern "C" __global__ void pad_nhwc_kernel(
 // measured ~0.53 ms/step). Folded in the epilogue via LDS atomics into
 // the dead staging buffers; disjoint column ranges per block, so the
 // partial rows need no zero-init and no global atomics.
-template <int BM, int BN, int WAVES_M, int WAVES_N, bool GROUPED = false>
+// AFF (0 = off, 1 = affine, 2 = affine + relu; never with split-K or
+// BN_PART): the eval-mode BN(+ReLU) of the following layer folded into the
+// epilogue on the bf16-ROUNDED accumulator, bit for bit this kernel followed
+// by bnrelu.hip's bn_apply_kernel:
+//   C = bf16(relu?(fmaf(float(bf16(acc)), scale[n], shift[n])))
+// scale/shift (fp32 [N]) are loaded into registers ahead of the K loop.
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool GROUPED = false,
+          int AFF = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_kernel(
     const bf16* __restrict__ XP, const bf16* __restrict__ B,
     bf16* __restrict__ C_out, const int M, const int N, const int Cin,
     const int HW_out, const int W_out, const int Hp, const int Wp,
     const int stride_hw, const int gw = 0,
     float* __restrict__ C_part = nullptr,
-    float* __restrict__ bn_part = nullptr) {
+    float* __restrict__ bn_part = nullptr,
+    const float* __restrict__ bn_scale = nullptr,
+    const float* __restrict__ bn_shift = nullptr) {
   constexpr int BK = 64;
   constexpr int A_BYTES = BM * BK * 2;
   constexpr int B_BYTES = BN * BK * 2;
@@ -177,6 +186,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(
     if (kt0 >= kt1) return;
   }
   stage(kt0 & 1, kt0);
+  // AFF: the lane's 4 + 4 scale/shift values (columns n0 + wn + nf*16 +
+  // (lane & 15)), issued here so the epilogue waits on nothing
+  float aff_sc[4], aff_sh[4];
+  if constexpr (AFF != 0) {
+#pragma unroll
+    for (int nf = 0; nf < 4; ++nf) {
+      aff_sc[nf] = bn_scale[n0 + wn + nf * 16 + (lane & 15)];
+      aff_sh[nf] = bn_shift[n0 + wn + nf * 16 + (lane & 15)];
+    }
+  }
   __syncthreads();
   for (int kt = kt0; kt < kt1; ++kt) {
     const int cur = kt & 1;
@@ -200,6 +219,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(
 
   const int cn = lane & 15;
   const int r4 = (lane >> 4) * 4;
+  if constexpr (AFF != 0) {
+#pragma unroll
+    for (int mf = 0; mf < 4; ++mf) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int m = m0 + wm + mf * 16 + r4 + reg;
+        if (m < M) {
+          bf16* crow = C_out + (long long)m * N + n0 + wn + cn;
+#pragma unroll
+          for (int nf = 0; nf < 4; ++nf) {
+            const bf16 yb = __float2bfloat16(acc[mf][nf][reg]);
+            float v = fmaf(__bfloat162float(yb), aff_sc[nf], aff_sh[nf]);
+            if constexpr (AFF == 2) v = fmaxf(v, 0.0f);
+            crow[nf * 16] = __float2bfloat16(v);
+          }
+        }
+      }
+    }
+    return;
+  }
   // local per-column stats accumulators (summed into LDS afterwards)
   float ls[4] = {0, 0, 0, 0}, lq[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -744,6 +783,31 @@ extern "C" void launch_conv3x3_grouped(const void* xp, const void* w3g, void* y,
                      (bf16*)y, M, Cout, Cin, HW_out, W_out, Hp, Wp, stride, gw);
 }
 
+// launch_conv3x3_grouped with the eval BN(+ReLU) apply in the epilogue:
+// y = bf16(relu?(fma(float(bf16(conv)), scale[c], shift[c]))), scale/shift
+// fp32 [Cout]
+extern "C" void launch_conv3x3_grouped_bn(const void* xp, const void* w3g,
+                                          void* y, int M, int Cout, int Cin,
+                                          int HW_out, int W_out, int Hp,
+                                          int Wp, int stride, int gw,
+                                          const float* scale,
+                                          const float* shift, bool relu,
+                                          hipStream_t s) {
+  constexpr int BM = 256, BN = 64;
+  const int grid = ((M + BM - 1) / BM) * (Cout / BN);
+  const int lds_bytes = 2 * (BM * 64 * 2 + BN * 64 * 2);
+  if (relu)
+    hipLaunchKernelGGL((conv3x3_kernel<BM, BN, 4, 1, true, 2>), dim3(grid),
+                       dim3(256), lds_bytes, s, (const bf16*)xp,
+                       (const bf16*)w3g, (bf16*)y, M, Cout, Cin, HW_out, W_out,
+                       Hp, Wp, stride, gw, nullptr, nullptr, scale, shift);
+  else
+    hipLaunchKernelGGL((conv3x3_kernel<BM, BN, 4, 1, true, 1>), dim3(grid),
+                       dim3(256), lds_bytes, s, (const bf16*)xp,
+                       (const bf16*)w3g, (bf16*)y, M, Cout, Cin, HW_out, W_out,
+                       Hp, Wp, stride, gw, nullptr, nullptr, scale, shift);
+}
+
 extern "C" int conv3x3_pick_splitk(int M, int Cout, int Cin) {
   // split only CU-starved deep-K launches (stage 3/4 at bs32: 52-98
   // tiles, K 2304-4608); aim for ~384-512 total blocks
@@ -788,4 +852,28 @@ extern "C" void launch_conv3x3(const void* xp, const void* w3, void* y, int M,
                        Hp, Wp, stride, 0, splitk > 1 ? cpart : nullptr,
                        bn_part);
   }
+}
+
+// launch_conv3x3's non-split route with the eval BN(+ReLU) apply in the
+// epilogue (see conv3x3_kernel AFF); the caller sends split-K shapes through
+// launch_conv3x3 + cast + launch_bn_apply instead. scale/shift fp32 [Cout]
+extern "C" void launch_conv3x3_bn(const void* xp, const void* w3, void* y,
+                                  int M, int Cout, int Cin, int HW_out,
+                                  int W_out, int Hp, int Wp, int stride,
+                                  const float* scale, const float* shift,
+                                  bool relu, hipStream_t s) {
+#define CBN_CASE(BM, BN, WM, WN, AFF)                                         \
+  hipLaunchKernelGGL((conv3x3_kernel<BM, BN, WM, WN, false, AFF>),            \
+                     dim3(((M + BM - 1) / BM) * (Cout / BN)), dim3(256),      \
+                     2 * (BM * 64 * 2 + BN * 64 * 2), s, (const bf16*)xp,     \
+                     (const bf16*)w3, (bf16*)y, M, Cout, Cin, HW_out, W_out,  \
+                     Hp, Wp, stride, 0, nullptr, nullptr, scale, shift)
+  if (Cout % 128 == 0) {
+    if (relu) CBN_CASE(128, 128, 2, 2, 2);
+    else CBN_CASE(128, 128, 2, 2, 1);
+  } else {
+    if (relu) CBN_CASE(256, 64, 4, 1, 2);
+    else CBN_CASE(256, 64, 4, 1, 1);
+  }
+#undef CBN_CASE
 }

@@ -23,6 +23,10 @@
 //     residual-gradient add of the 1x1 dgrad folded in; R reaches the lanes
 //     through the staging buffer that is dead in the last K-tile (RADD 1) or
 //     by plain 2-byte global loads (RADD 2, the measured alternative)
+//   * AFF epilogue (launch_gemm_bt_bn): the eval-mode BN(+Add)+ReLU of the
+//     following layer folded in, C = bf16(relu?(fma(float(bf16(acc)), scale,
+//     shift) [+ R])); scale/shift are loaded into registers before the K
+//     loop, R takes the RADD 1 route
 #include "common.h"
 #include "launchers.h"
 
@@ -33,11 +37,13 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool SPLITK = false,
-          bool V2 = false, int RADD = 0>
+          bool V2 = false, int RADD = 0, int AFF = 0>
 __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     void* __restrict__ C_any, const int M, const int N, const int K,
-    float* __restrict__ bn_part = nullptr, const int ldsb = 0) {
+    float* __restrict__ bn_part = nullptr, const int ldsb = 0,
+    const float* __restrict__ bn_scale = nullptr,
+    const float* __restrict__ bn_shift = nullptr) {
   // bn_part: per-channel sum/sumsq partials of the bf16-rounded output,
   // [tiles_m, 2N] — lets the following BatchNorm skip its stats kernel
   // (see conv3x3.hip BN_PART)
@@ -48,7 +54,19 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   // (no stats with it, so the existing kernels keep their argument list):
   // C = bf16(float(bf16(acc)) + float(R)) — the accumulator is rounded to
   // bf16 FIRST, which is bit-for-bit gemm_bt followed by a bf16 add.
+  // AFF (0 = off, else 1 + relu + 2*residual): the per-channel eval affine
+  // of bnrelu.hip apply_octet on the bf16-ROUNDED accumulator, bit for bit
+  // gemm_bt followed by bn_apply_kernel:
+  //   v = fmaf(float(bf16(acc)), scale[n], shift[n]); v += float(R) with a
+  //   residual; v = fmaxf(v, 0) with relu; C = bf16(v)
+  // scale/shift: fp32 [N]. The residual travels and is staged like RADD 1's
+  // R (bn_part slot, stage_r).
   static_assert(RADD == 0 || (!SPLITK && !V2), "RADD: plain bf16 loop only");
+  static_assert(AFF == 0 || (!SPLITK && !V2 && RADD == 0),
+                "AFF: plain bf16 loop only");
+  constexpr bool AFF_RELU = AFF != 0 && ((AFF - 1) & 1);
+  constexpr bool AFF_RES = AFF != 0 && ((AFF - 1) & 2);
+  constexpr bool STAGE_R = RADD == 1 || AFF_RES;  // R through the dead buffer
   bf16* C = SPLITK ? nullptr : (bf16*)C_any;
   float* Cf = SPLITK ? (float*)C_any : nullptr;
   constexpr int BK = 64;
@@ -155,7 +173,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
     }
   };
 
-  // RADD 1: each wave stages ITS 64x64 sub-tile of R (8 KiB, 8 glds) into
+  // STAGE_R: each wave stages ITS 64x64 sub-tile of R (8 KiB, 8 glds) into
   // its own slice of staging buffer `buf`; it alone reads that slice back.
   // LDS image: row r at r*128, 16-B slot s holds global slot s ^ f(r) with
   // f(r) = ((r >> 2) & 3) << 1 — the four rows (lane>>4)*4 + reg that one
@@ -189,8 +207,18 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   // buffer (K/BK)&1 never receives another A/B tile once the last K-tile
   // is being computed; with ONE K-tile it is free from the start and R
   // rides along with the first stage
-  if constexpr (RADD == 1)
+  if constexpr (STAGE_R)
     if (kt_end == 1) stage_r(1);
+  // AFF: the lane's 4 + 4 scale/shift values (columns n0 + wn + nf*16 +
+  // (lane & 15)), issued ahead of the K loop so the epilogue waits on nothing
+  float aff_sc[4], aff_sh[4];
+  if constexpr (AFF != 0) {
+#pragma unroll
+    for (int nf = 0; nf < 4; ++nf) {
+      aff_sc[nf] = bn_scale[n0 + wn + nf * 16 + (lane & 15)];
+      aff_sh[nf] = bn_shift[n0 + wn + nf * 16 + (lane & 15)];
+    }
+  }
   __syncthreads();
 
   // v2 main loop: 4 phases per K-tile — each phase prefetches a quarter of
@@ -228,7 +256,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   for (int kt = kt_begin; kt < kt_end; ++kt) {
     const int cur = (kt - kt_begin) & 1;
     if (kt + 1 < kt_end) stage(cur ^ 1, kt + 1);
-    else if constexpr (RADD == 1) {
+    else if constexpr (STAGE_R) {
       // last tile: R lands under its MFMAs; the closing __syncthreads
       // (vmcnt(0) + barrier) retires it before the epilogue reads
       if (kt_end > 1) stage_r(cur ^ 1);
@@ -254,6 +282,35 @@ __global__ __launch_bounds__(256, 2) void gemm_bt_kernel(
   // row=(lane>>4)*4+reg ----
   const int cn = lane & 15;
   const int r4 = (lane >> 4) * 4;
+  if constexpr (AFF != 0) {
+    const char* rbase =
+        lds + ((K / BK) & 1) * (A_BYTES + B_BYTES) + wave * 8192;
+#pragma unroll
+    for (int mf = 0; mf < 4; ++mf) {
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int r = mf * 16 + r4 + reg;
+        const int m = m0 + wm + r;
+        if (m < M) {
+          bf16* crow = C + (long long)m * N + n0 + wn + cn;
+#pragma unroll
+          for (int nf = 0; nf < 4; ++nf) {
+            const bf16 yb = __float2bfloat16(acc[mf][nf][reg]);
+            float v = fmaf(__bfloat162float(yb), aff_sc[nf], aff_sh[nf]);
+            if constexpr (AFF_RES) {
+              const int c = nf * 16 + cn;  // stage_r's LDS image
+              v += __bfloat162float(*(const bf16*)(
+                  rbase + r * 128 +
+                  (((c >> 3) ^ (((r >> 2) & 3) << 1)) << 4) + (c & 7) * 2));
+            }
+            if constexpr (AFF_RELU) v = fmaxf(v, 0.0f);
+            crow[nf * 16] = __float2bfloat16(v);
+          }
+        }
+      }
+    }
+    return;
+  }
   if constexpr (RADD != 0) {
     const bf16* R = (const bf16*)bn_part;
     const char* rbase =
@@ -493,6 +550,37 @@ extern "C" void launch_gemm_bt_add(const void* A, const void* B, const void* R,
                          dim3(grid), dim3(256), lds_bytes, s, (const bf16*)A,
                          (const bf16*)B, C, M, N, K, r, 0);
   }
+}
+
+// C = bf16(relu?(fma(float(bf16(A @ B^T)), scale[n], shift[n]) [+ R])): gemm_bt
+// followed by the eval BN(+Add)+ReLU apply, bit for bit. R bf16 [M, N] laid
+// out like C, or null; scale, shift fp32 [N]
+extern "C" void launch_gemm_bt_bn(const void* A, const void* B, const void* R,
+                                  void* C, int M, int N, int K,
+                                  const float* scale, const float* shift,
+                                  bool relu, hipStream_t s) {
+  // R travels in the bn_part slot (never dereferenced as float)
+  float* r = (float*)const_cast<void*>(R);
+  const int aff = 1 + (relu ? 1 : 0) + (R != nullptr ? 2 : 0);
+#define BN_CASE(BM, BN, WM, WN, AFF)                                          \
+  hipLaunchKernelGGL((gemm_bt_kernel<BM, BN, WM, WN, false, false, 0, AFF>),  \
+                     dim3(((M + BM - 1) / BM) * (N / BN)), dim3(256),         \
+                     2 * (BM * 64 * 2 + BN * 64 * 2), s, (const bf16*)A,      \
+                     (const bf16*)B, C, M, N, K, r, 0, scale, shift)
+#define BN_TILE(BM, BN, WM, WN)                  \
+  switch (aff) {                                 \
+    case 1: BN_CASE(BM, BN, WM, WN, 1); break;   \
+    case 2: BN_CASE(BM, BN, WM, WN, 2); break;   \
+    case 3: BN_CASE(BM, BN, WM, WN, 3); break;   \
+    default: BN_CASE(BM, BN, WM, WN, 4); break;  \
+  }
+  if (N % 128 == 0) {
+    BN_TILE(128, 128, 2, 2)
+  } else {  // N % 64 == 0
+    BN_TILE(256, 64, 4, 1)
+  }
+#undef BN_TILE
+#undef BN_CASE
 }
 
 extern "C" void launch_gemm_bt_splitk(const void* A, const void* B, float* Cf32,

@@ -175,6 +175,12 @@ void launch_gemm_bt(const void* A, const void* B, void* C, int M, int N,
 // C = bf16(float(bf16(A @ B^T)) + float(R)), R bf16 [M, N] laid out like C
 void launch_gemm_bt_add(const void* A, const void* B, const void* R, void* C,
                         int M, int N, int K, hipStream_t s);
+// C = bf16(relu?(fma(float(bf16(A @ B^T)), scale[n], shift[n]) [+ R])): the
+// eval BN(+Add)+ReLU apply in the epilogue. R (bf16 [M, N] like C, or null)
+// comes BEFORE C as in launch_gemm_bt_add; scale, shift fp32 [N] after K
+void launch_gemm_bt_bn(const void* A, const void* B, const void* R, void* C,
+                       int M, int N, int K, const float* scale,
+                       const float* shift, bool relu, hipStream_t s);
 void launch_gemm_bt_splitk(const void* A, const void* B, float* Cf32, int M,
                            int N, int K, int splitk, hipStream_t s);
 
@@ -195,6 +201,17 @@ void launch_conv3x3(const void* xp, const void* w3, void* y, int M, int Cout,
 void launch_conv3x3_grouped(const void* xp, const void* w3g, void* y, int M,
                             int Cout, int Cin, int HW_out, int W_out, int Hp,
                             int Wp, int stride, int gw, hipStream_t s);
+// the _bn twins: the eval BN(+ReLU) apply in the epilogue, non-split only;
+// scale, shift (fp32 [Cout]) and relu follow the geometry (and gw)
+void launch_conv3x3_bn(const void* xp, const void* w3, void* y, int M,
+                       int Cout, int Cin, int HW_out, int W_out, int Hp,
+                       int Wp, int stride, const float* scale,
+                       const float* shift, bool relu, hipStream_t s);
+void launch_conv3x3_grouped_bn(const void* xp, const void* w3g, void* y,
+                               int M, int Cout, int Cin, int HW_out,
+                               int W_out, int Hp, int Wp, int stride, int gw,
+                               const float* scale, const float* shift,
+                               bool relu, hipStream_t s);
 void launch_conv3x3_small(const void* xp, const void* w3s, void* y, int M,
                           int Cout_real, int cpt, int HW_out, int W_out,
                           int Hp, int Wp, int stride, float* bn_part,

@@ -1035,6 +1035,55 @@ torch::Tensor gemm_bt_add(torch::Tensor a, torch::Tensor b, torch::Tensor r) {
   return c;
 }
 
+// the eval-BN epilogue operands: scale, shift fp32 [N], dense, on like's
+// device
+void check_bn_affine(const torch::Tensor& scale, const torch::Tensor& shift,
+                     int64_t N, const torch::Tensor& like, const char* who) {
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat32 &&
+                  shift.scalar_type() == torch::kFloat32,
+              who, ": scale/shift fp32 only");
+  TORCH_CHECK(scale.is_cuda() && shift.is_cuda() &&
+                  scale.device() == like.device() &&
+                  shift.device() == like.device(),
+              who, ": scale/shift on another device than the input");
+  TORCH_CHECK(scale.dim() == 1 && shift.dim() == 1 && scale.size(0) == N &&
+                  shift.size(0) == N,
+              who, ": scale/shift shape [N] required, N = ", N);
+  TORCH_CHECK(scale.is_contiguous() && shift.is_contiguous(), who,
+              ": scale/shift not contiguous");
+}
+
+// y = bf16(relu?(fma(float(bf16(A @ B^T)), scale[n], shift[n]) [+ res])):
+// gemm_bt followed by bn_fwd_eval, bit for bit, in one kernel (conv1x1 ->
+// eval BN(+Add)+ReLU). res is read in place and never written.
+torch::Tensor gemm_bt_bn(torch::Tensor a, torch::Tensor b, torch::Tensor scale,
+                         torch::Tensor shift, bool relu,
+                         c10::optional<torch::Tensor> res) {
+  check_bt_operands(a, b, "gemm_bt_bn");
+  const int M = (int)a.size(0), K = (int)a.size(1), N = (int)b.size(0);
+  check_bn_affine(scale, shift, N, a, "gemm_bt_bn");
+  if (res.has_value()) {
+    const torch::Tensor& r = *res;
+    TORCH_CHECK(r.scalar_type() == torch::kBFloat16,
+                "gemm_bt_bn: res bf16 only");
+    TORCH_CHECK(r.is_cuda() && r.device() == a.device(),
+                "gemm_bt_bn: res on another device than a");
+    TORCH_CHECK(r.dim() == 2 && r.size(0) == M && r.size(1) == N,
+                "gemm_bt_bn: res shape [M, N] required");
+    TORCH_CHECK(r.is_contiguous(), "gemm_bt_bn: res not contiguous");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(r.data_ptr()) % 16 == 0,
+                "gemm_bt_bn: res base not 16-byte aligned");
+  }
+  auto ac = a.contiguous();
+  auto bc = b.contiguous();
+  auto c = torch::empty({M, N}, a.options());
+  launch_gemm_bt_bn(ac.data_ptr(), bc.data_ptr(),
+                    res.has_value() ? res->data_ptr() : nullptr, c.data_ptr(),
+                    M, N, K, scale.data_ptr<float>(), shift.data_ptr<float>(),
+                    relu, cur_stream());
+  return c;
+}
+
 // flat zero-halo padded copy of x [N, C, H, W] channels_last bf16, widened
 // to cpad >= C channels: N * (H+2) * (W+2) * cpad elements
 torch::Tensor pad_nhwc_flat(const torch::Tensor& x, int cpad, hipStream_t s) {
@@ -1051,8 +1100,11 @@ torch::Tensor pad_nhwc_flat(const torch::Tensor& x, int cpad, hipStream_t s) {
   return xp;
 }
 
-torch::Tensor conv3x3_grouped_fwd(torch::Tensor x, torch::Tensor w3g,
-                                  int64_t stride) {
+// scale/shift given: the eval BN(+ReLU) apply rides in the kernel epilogue
+torch::Tensor conv3x3_grouped_impl(const torch::Tensor& x,
+                                   const torch::Tensor& w3g, int64_t stride,
+                                   const torch::Tensor* scale,
+                                   const torch::Tensor* shift, bool relu) {
   // grouped 3x3: w3g [Cout, 9*gw] where gw = the gemm group width —
   // channels-per-group when >= 64 (exact, zero wasted MFMA), else 64
   // with a block-diagonal zero-padded repack (conv.py _repack_w3_grouped)
@@ -1065,15 +1117,34 @@ torch::Tensor conv3x3_grouped_fwd(torch::Tensor x, torch::Tensor w3g,
   TORCH_CHECK(gw % 64 == 0 && Cin % gw == 0, "conv3x3g: gw % 64, Cin % gw");
   TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0 && Cin == Cout,
               "conv3x3g: C % 64, equal in/out");
+  if (scale != nullptr)
+    check_bn_affine(*scale, *shift, Cout, x, "conv3x3g_bn");
   const int Hout = out_extent(H, stride), Wout = out_extent(W, stride);
   const long long M = (long long)Nimg * Hout * Wout;
   auto s = cur_stream();
   auto xp = pad_nhwc_flat(x, Cin, s);
   auto y = torch::empty({M, Cout}, x.options());
-  launch_conv3x3_grouped(xp.data_ptr(), w3g.data_ptr(), y.data_ptr(), (int)M,
-                         Cout, Cin, Hout * Wout, Wout, H + 2, W + 2,
-                         (int)stride, gw, s);
+  if (scale != nullptr)
+    launch_conv3x3_grouped_bn(xp.data_ptr(), w3g.data_ptr(), y.data_ptr(),
+                              (int)M, Cout, Cin, Hout * Wout, Wout, H + 2,
+                              W + 2, (int)stride, gw, scale->data_ptr<float>(),
+                              shift->data_ptr<float>(), relu, s);
+  else
+    launch_conv3x3_grouped(xp.data_ptr(), w3g.data_ptr(), y.data_ptr(),
+                           (int)M, Cout, Cin, Hout * Wout, Wout, H + 2, W + 2,
+                           (int)stride, gw, s);
   return y;
+}
+
+torch::Tensor conv3x3_grouped_fwd(torch::Tensor x, torch::Tensor w3g,
+                                  int64_t stride) {
+  return conv3x3_grouped_impl(x, w3g, stride, nullptr, nullptr, false);
+}
+
+torch::Tensor conv3x3_grouped_fwd_bn(torch::Tensor x, torch::Tensor w3g,
+                                     int64_t stride, torch::Tensor scale,
+                                     torch::Tensor shift, bool relu) {
+  return conv3x3_grouped_impl(x, w3g, stride, &scale, &shift, relu);
 }
 
 // stem conv (small channels): x [N, Cin, H, W] channels_last bf16 with
@@ -1466,6 +1537,33 @@ std::vector<torch::Tensor> conv3x3_fwd_stats_padded(torch::Tensor xp,
   return conv3x3_fwd_impl(xp, w3, stride, H, W, true);
 }
 
+// conv3x3_fwd_padded followed by bn_fwd_eval (no residual), bit for bit.
+// Non-split shapes run the fused epilogue; split-K shapes run the split-K
+// launch and the cast as above, then the BN apply kernel on the result, so
+// the caller never has to know the pick.
+torch::Tensor conv3x3_fwd_bn_padded(torch::Tensor xp, torch::Tensor w3,
+                                    int64_t stride, int64_t H, int64_t W,
+                                    torch::Tensor scale, torch::Tensor shift,
+                                    bool relu) {
+  const Conv3x3Geom g = conv3x3_geom(xp, w3, stride, H, W);
+  check_bn_affine(scale, shift, g.Cout, xp, "conv3x3_bn");
+  const int M = (int)g.M;
+  auto s = cur_stream();
+  if (conv3x3_pick_splitk(M, g.Cout, g.Cin) > 1) {
+    auto y0 = conv3x3_fwd_impl(xp, w3, stride, H, W, false)[0];
+    auto y = torch::empty_like(y0);
+    launch_bn_apply(y0.data_ptr(), nullptr, y.data_ptr(), nullptr,
+                    scale.data_ptr<float>(), shift.data_ptr<float>(), g.M,
+                    g.Cout, relu, false, s);
+    return y;
+  }
+  auto y = torch::empty({g.M, g.Cout}, xp.options());
+  launch_conv3x3_bn(xp.data_ptr(), w3.data_ptr(), y.data_ptr(), M, g.Cout,
+                    g.Cin, g.Hout * g.Wout, g.Wout, g.Hp, g.Wp, (int)stride,
+                    scale.data_ptr<float>(), shift.data_ptr<float>(), relu, s);
+  return y;
+}
+
 // the unpadded twins: x 4-D channels_last bf16 [N, C, H, W], padded here
 torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
   check_nhwc_bf16(x, "conv3x3", 64);
@@ -1711,6 +1809,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_bt_add", &gemm_bt_add,
         "gemm_bt with a bf16 [M,N] addend: bf16(float(bf16(A@B^T)) + R)",
         py::arg("a"), py::arg("b"), py::arg("r"));
+  m.def("gemm_bt_bn", &gemm_bt_bn, py::arg("a"), py::arg("b"),
+        py::arg("scale"), py::arg("shift"), py::arg("relu"),
+        py::arg("res") = py::none(),
+        "gemm_bt + eval BN(+Add)+ReLU apply in one kernel, bit-equal to "
+        "bn_fwd_eval(gemm_bt(a, b), scale, shift, res, relu)");
+  m.def("conv3x3_fwd_bn_padded", &conv3x3_fwd_bn_padded,
+        "conv3x3_fwd_padded + eval BN(+ReLU) apply: (xp, w3, stride, H, W, "
+        "scale, shift, relu) -> y2d; fused epilogue on non-split shapes");
+  m.def("conv3x3_grouped_fwd_bn", &conv3x3_grouped_fwd_bn,
+        "conv3x3_grouped_fwd + eval BN(+ReLU) apply in the epilogue: (x, "
+        "w3g, stride, scale, shift, relu) -> y2d");
   m.def("transpose_pad", &transpose_pad,
         "bf16 [M,C] -> [C, ceil64(M)] transpose with zero pad");
   m.def("gemm_bt_splitk", &gemm_bt_splitk,

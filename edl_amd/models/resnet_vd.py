@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 
 from ..ops.bnrelu import BNAddReLU2d, BNReLU2d
-from ..ops.conv import Conv2dFast
+from ..ops.conv import Conv2dFast, conv_bn, eval_pair
 from ..ops.pool import AvgPool2x2, MaxPool3x3s2
 
 
@@ -34,6 +34,11 @@ class ConvBN(nn.Module):
         # dy from the BN backward in the padded layout (dx_pad).
         # pad_out: the caller feeds the result to exactly one 3x3
         # Conv2dFast — the BN writes that conv's padded input layout.
+        # Inference: conv and BN as one kernel where both are in-repo
+        # (ops.conv.conv_bn); none of the hand-offs above exists there.
+        if eval_pair(self.bn):
+            y = conv_bn(self.conv, self.bn, x)
+            return (y, x) if fork else y
         x_fork = None
         if fork:
             y, x_fork = self.conv(x, bn_stats=self.bn.training, dx_pad=True,
@@ -89,6 +94,8 @@ class BottleneckVd(nn.Module):
         y0, x_fork = self.conv0(x, pad_out=self.conv1.conv.takes_padded(),
                                 fork=True)
         s = self.shortcut(x_fork)
+        if eval_pair(self.bn_add):  # inference: conv2 + bn_add in one kernel
+            return conv_bn(self.conv2, self.bn_add, self.conv1(y0), s)
         y = self.conv2(self.conv1(y0), bn_stats=self.bn_add.training)
         return self.bn_add(y, s, partials=self.conv2.pop_bn_part())
 

@@ -8,8 +8,17 @@ CDNA4 kernels (edl_amd.ops.bnrelu) on GPU."""
 import torch.nn as nn
 
 from ..ops.bnrelu import BNAddReLU2d, BNReLU2d
-from ..ops.conv import Conv2dFast
+from ..ops.conv import Conv2dFast, conv_bn
 from ..ops.pool import MaxPool3x3s2
+
+
+class _Downsample(nn.Sequential):
+    """The projection shortcut, conv "0" then BN "1" (the nn.Sequential
+    child names, so state-dict keys stay downsample.0.* / downsample.1.*),
+    run as one conv_bn pair."""
+
+    def forward(self, x):
+        return conv_bn(self[0], self[1], x)
 
 
 class ResNeXtBottleneck(nn.Module):
@@ -28,16 +37,18 @@ class ResNeXtBottleneck(nn.Module):
         self.bn_add = BNAddReLU2d(cout)
         self.downsample = None
         if stride != 1 or cin != cout:
-            self.downsample = nn.Sequential(
+            self.downsample = _Downsample(
                 Conv2dFast(cin, cout, 1, stride=stride, bias=False),
                 BNReLU2d(cout, act=False),
             )
 
     def forward(self, x):
         s = x if self.downsample is None else self.downsample(x)
-        y = self.bn1(self.conv1(x))
-        y = self.bn2(self.conv2(y))
-        return self.bn_add(self.conv3(y), s)
+        # conv_bn: bn(conv(x)[, s]); in inference one kernel per pair where
+        # both halves are in-repo kernels
+        y = conv_bn(self.conv1, self.bn1, x)
+        y = conv_bn(self.conv2, self.bn2, y)
+        return conv_bn(self.conv3, self.bn_add, y, s)
 
 
 class ResNeXtWSL(nn.Module):

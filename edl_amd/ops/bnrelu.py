@@ -122,11 +122,19 @@ class BNReLU2d(nn.Module):
         self._batches_seen = int(self.num_batches_tracked.item())
 
     def _use_fused(self, x, res=None):
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and available()):
+            return False
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            return False
+        return self._fused_applies(res)
+
+    def _fused_applies(self, res=None):
+        """The part of _use_fused that does not look at x: what the module,
+        the mode and the residual allow for a bf16 channels_last GPU input
+        (ops.conv.conv_bn asks before the conv output exists)."""
         import os
 
         if os.environ.get("EDL_FUSED_BN", "1") != "1":
-            return False
-        if not (x.is_cuda and x.dtype == torch.bfloat16 and available()):
             return False
         if self.num_features % 8 != 0:
             return False
@@ -139,8 +147,6 @@ class BNReLU2d(nn.Module):
             if (self.training or torch.is_grad_enabled() or
                     (wide and os.environ.get("EDL_BN_WIDE_EVAL", "0") != "1")):
                 return False
-        if not x.is_contiguous(memory_format=torch.channels_last):
-            return False
         if res is not None and (
             res.dtype != torch.bfloat16
             or not res.is_contiguous(memory_format=torch.channels_last)
@@ -185,25 +191,32 @@ class BNReLU2d(nn.Module):
                 self.momentum, self.eps, res2d, self.act, partials,
             )
         else:
-            # eval scale/shift depend only on (weight, bias, running
-            # stats): cache them keyed on the tensors' in-place versions.
-            # Recomputing per forward cost ~4 tiny kernels x ~104 BN
-            # layers per ResNeXt101 teacher fwd (~300 ms/s of pure launch
-            # + elementwise overhead in the distill teacher trace r2c41).
-            # The version key does NOT see kernel writes (bn_fwd_train,
-            # fused_sgd, graph replay go through raw pointers):
-            # TrainerEngine.evaluate() invalidates _eval_ver explicitly.
-            ver = (self.weight._version, self.bias._version,
-                   self.running_mean._version, self.running_var._version)
-            if getattr(self, "_eval_ver", None) != ver:
-                invstd = torch.rsqrt(self.running_var + self.eps)
-                scale = self.weight * invstd
-                self._eval_scale = scale
-                self._eval_shift = self.bias - self.running_mean * scale
-                self._eval_ver = ver
-            y2d = ext().bn_fwd_eval(x2d, self._eval_scale,
-                                    self._eval_shift, res2d, self.act)
+            scale, shift = self.eval_scale_shift()
+            y2d = ext().bn_fwd_eval(x2d, scale, shift, res2d, self.act)
         return _from_2d(y2d, x.shape)
+
+    def eval_scale_shift(self):
+        """(scale, shift), fp32 [C]: the eval-mode BN as y = x*scale + shift.
+
+        They depend only on (weight, bias, running stats) and are cached,
+        keyed on the four tensors' device, data_ptr() and in-place versions
+        (a .to() or a replaced parameter gives fresh tensors whose versions
+        restart, so the versions alone can collide). Recomputing per forward
+        cost ~4 tiny kernels x ~104 BN layers per ResNeXt101 teacher fwd
+        (~300 ms/s of pure launch + elementwise overhead in the distill
+        teacher trace r2c41). The key does NOT see kernel writes
+        (bn_fwd_train, fused_sgd, graph replay go through raw pointers):
+        TrainerEngine.evaluate() invalidates _eval_ver explicitly."""
+        ver = tuple((t.device, t.data_ptr(), t._version)
+                    for t in (self.weight, self.bias, self.running_mean,
+                              self.running_var))
+        if getattr(self, "_eval_ver", None) != ver:
+            invstd = torch.rsqrt(self.running_var + self.eps)
+            scale = self.weight * invstd
+            self._eval_scale = scale
+            self._eval_shift = self.bias - self.running_mean * scale
+            self._eval_ver = ver
+        return self._eval_scale, self._eval_shift
 
     def forward(self, x, res=None, partials=None, pad_out=False, dx_pad=None):
         # partials: BN stats pre-folded into the producing conv's

@@ -132,6 +132,13 @@ _GROUPED_MINC = int(os.environ.get("EDL_CONV3X3_GROUPED_MINC", "16"))
 # skips its stats kernel — a full activation re-read, ~0.53 ms/step).
 _BN_STATS_FUSED = os.environ.get("EDL_BN_STATS_FUSED", "1") == "1"
 
+# Inference (module in eval(), autograd off): a conv whose output feeds one
+# fused BN(+Add)+ReLU runs that BN's per-channel scale/shift (+ residual,
+# + ReLU) in its own GEMM epilogue (conv_bn below) instead of a bn_apply
+# launch that re-reads and re-writes the activation. Bit-equal to the pair of
+# kernels it replaces. 0 = the two launches, as before.
+_EVAL_FUSE = os.environ.get("EDL_EVAL_FUSE", "1") == "1"
+
 # Zero-halo padded buffers [N, H+2, W+2, C] of the 3x3 implicit-GEMM path.
 # Each stage keeps its own opt-out (0 = the previous behaviour):
 #  EDL_PAD_ONCE   the conv pads its input ONCE in forward and saves the
@@ -767,3 +774,119 @@ class Conv2dFast(nn.Conv2d):
         if fork:
             return _nchw_view(y2d, n, h, w), _nchw_view(xf2d, n, h, w)
         return _nchw_view(y2d, n, h, w)
+
+    # ---- conv -> eval BN in one kernel (conv_bn) ----
+
+    def _eval_bn_route(self, x):
+        """Which in-repo kernel forward(x) would run on this bf16 GPU input
+        with autograd off, among those that carry the BN epilogue: "1x1",
+        "dense3x3", "grouped3x3", or None (the stem kernels, MIOpen, the
+        matmul route). Mirrors the order of the checks in forward."""
+        if not (x.is_cuda and available() and x.dtype == torch.bfloat16
+                and x.dim() == 4):
+            return None
+        if _CONV3X3 == "hip":
+            if self._is_dense3x3():
+                return "dense3x3"
+            if (os.environ.get("EDL_CONV3X3_SMALL", "1") == "1"
+                    and self._is_small3x3()):
+                return None
+            if self._is_grouped3x3():
+                return "grouped3x3"
+        if (_CONV1X1 == "hip" and self.kernel_size == (1, 1)
+                and self.groups == 1 and self.padding == (0, 0)
+                and self.bias is None and self.in_channels % 64 == 0
+                and self.out_channels % 64 == 0):
+            return "1x1"
+        return None
+
+    def _forward_bn(self, route, x, scale, shift, relu, res):
+        """forward(x) with y*scale + shift (+ res) (+ ReLU) in the kernel
+        epilogue; the operands are prepared as the _forward_* of the route
+        prepares them. No autograd: inference only."""
+        e = ext()
+        co, ci = self.out_channels, self.in_channels
+        mb = getattr(self.weight, "_edl_bf16", None)
+        if route == "1x1":
+            sh, sw = self.stride
+            if sh != 1 or sw != 1:
+                x = x[:, :, ::sh, ::sw]
+            if not x.is_contiguous(memory_format=torch.channels_last):
+                x = x.contiguous(memory_format=torch.channels_last)
+            n, _, h, w = x.shape
+            x2d = x.permute(0, 2, 3, 1).reshape(n * h * w, ci)
+            if mb is not None:
+                w_bf16 = mb.view(co, ci)
+            else:
+                w_bf16 = self._cached("w_bf16", lambda: self.weight.detach()
+                                      .view(co, ci).to(torch.bfloat16)
+                                      .contiguous())
+            res2d = None
+            if res is not None:
+                res2d = res.permute(0, 2, 3, 1).reshape(n * h * w, co)
+            y2d = e.gemm_bt_bn(x2d, w_bf16, scale, shift, relu, res2d)
+            return _nchw_view(y2d, n, h, w)
+        assert res is None  # the 3x3 epilogues carry no residual
+        n, _, h, w = x.shape
+        if route == "grouped3x3":
+            if not x.is_contiguous(memory_format=torch.channels_last):
+                x = x.contiguous(memory_format=torch.channels_last)
+            w3g = self._cached("w3g", lambda: _repack_w3_grouped(self.weight))
+            y2d = e.conv3x3_grouped_fwd_bn(x, w3g, self.stride[0], scale,
+                                           shift, relu)
+            return _nchw_view(y2d, n, *_out_hw(h, w, self.stride[0]))
+        # dense 3x3, as _forward_dense3x3: a padded buffer the preceding BN
+        # left on x is used only if x still IS its interior
+        xp = getattr(x, "_edl_xp", None) if _PAD_ONCE else None
+        if not is_interior_of(x, xp):
+            if not x.is_contiguous(memory_format=torch.channels_last):
+                x = x.contiguous(memory_format=torch.channels_last)
+            xp = e.pad_nhwc(x)
+        cl = getattr(self.weight, "_edl_phys_shape", None) is not None
+        if cl and mb is not None:
+            w3 = mb.permute(0, 2, 3, 1).reshape(co, 9 * ci)
+        else:
+            wsrc = mb if mb is not None else self.weight.detach()
+            w3 = self._cached("w3", lambda: _repack_w3(wsrc))
+        y2d = e.conv3x3_fwd_bn_padded(xp, w3, self.stride[0], h, w, scale,
+                                      shift, relu)
+        return _nchw_view(y2d, n, *_out_hw(h, w, self.stride[0]))
+
+
+def eval_pair(bn):
+    """True where a conv -> bn pair is inference and may go through conv_bn:
+    the BN in eval(), autograd off, EDL_EVAL_FUSE on."""
+    return _EVAL_FUSE and not bn.training and not torch.is_grad_enabled()
+
+
+def conv_bn(conv, bn, x, res=None):
+    """bn(conv(x), res), bit for bit: conv a Conv2dFast, bn a BNReLU2d (res
+    None) or BNAddReLU2d.
+
+    Exactly where that expression would run BOTH in-repo kernels in
+    inference — the conv on its hip route (1x1 at any stride, dense 3x3,
+    grouped 3x3) and the BN's fused eval apply — one kernel runs instead:
+    the conv with the BN's scale/shift (+ residual) (+ ReLU) in its epilogue.
+    The 3x3 kernels carry no residual. Everywhere else (training, autograd
+    on, CPU, fp32, the stem kernels, MIOpen routes, a BN on its torch
+    fallback, a residual the epilogue cannot read in place) the two modules
+    are called as written above."""
+    if eval_pair(bn) and bn.num_features == conv.out_channels:
+        route = conv._eval_bn_route(x)
+        if route is not None and res is not None:
+            n, _, h, w = x.shape
+            if route == "1x1":
+                ho, wo = -(-h // conv.stride[0]), -(-w // conv.stride[1])
+            else:
+                ho, wo = _out_hw(h, w, conv.stride[0])
+            if not (route == "1x1" and res.is_cuda
+                    and res.device == x.device
+                    and res.dtype == torch.bfloat16
+                    and tuple(res.shape) == (n, conv.out_channels, ho, wo)
+                    and res.is_contiguous(memory_format=torch.channels_last)
+                    and res.data_ptr() % 16 == 0):
+                route = None
+        if route is not None and bn._fused_applies(res):
+            scale, shift = bn.eval_scale_shift()
+            return conv._forward_bn(route, x, scale, shift, bn.act, res)
+    return bn(conv(x)) if res is None else bn(conv(x), res)

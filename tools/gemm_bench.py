@@ -2,6 +2,7 @@
 conv1x1 shapes at bs32. Run on a GPU box:
     python tools/gemm_bench.py
     python tools/gemm_bench.py --dgrad-add   # fused residual-add dgrad
+    python tools/gemm_bench.py --eval-bn     # conv1x1 + eval BN in one kernel
 """
 import os
 import sys
@@ -93,6 +94,33 @@ def main_wgrad3():
             t_bt / t_tn))
 
 
+def _graph_us(fn, sets, windows):
+    """Sorted us per call of fn(*set) over `windows` event-timed replays of
+    one graph-captured pass over the operand sets."""
+    for ops_ in sets:  # warm-up pass
+        fn(*ops_)
+    torch.cuda.synchronize()
+    # one pass over the sets as a graph: the step runs captured, so host
+    # launch cost must not count against a two-kernel variant
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for ops_ in sets:
+            fn(*ops_)
+    g.replay()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(windows):
+        t0 = torch.cuda.Event(enable_timing=True)
+        t1 = torch.cuda.Event(enable_timing=True)
+        t0.record()
+        g.replay()
+        t1.record()
+        torch.cuda.synchronize()
+        us.append(t0.elapsed_time(t1) * 1e3 / len(sets))
+    del g
+    return sorted(us)
+
+
 # (M, N=Cin, K=Cout, blocks) of the 16 BottleneckVd conv0 dgrads at bs32
 DGRAD_ADD_SHAPES = [
     (100352, 64, 64, 1), (100352, 256, 64, 2), (100352, 256, 128, 1),
@@ -128,29 +156,7 @@ def main_dgrad_add(windows=9, l3_bytes=256 << 20):
         }
         cols = []
         for key in ("a", "b", "c"):
-            fn = fns[key]
-            for a, b, r in sets:  # warm-up pass
-                fn(a, b, r)
-            torch.cuda.synchronize()
-            # one pass over the sets as a graph: the step runs captured,
-            # so host launch cost must not count against the two-kernel (a)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for a, b, r in sets:
-                    fn(a, b, r)
-            g.replay()
-            torch.cuda.synchronize()
-            us = []
-            for _ in range(windows):
-                t0 = torch.cuda.Event(enable_timing=True)
-                t1 = torch.cuda.Event(enable_timing=True)
-                t0.record()
-                g.replay()
-                t1.record()
-                torch.cuda.synchronize()
-                us.append(t0.elapsed_time(t1) * 1e3 / nsets)
-            del g
-            us.sort()
+            us = _graph_us(fns[key], sets, windows)
             med = us[len(us) // 2]
             tot[key] += med * cnt
             cols.append("%7.1f [%6.1f..%6.1f]" % (med, us[0], us[-1]))
@@ -161,9 +167,94 @@ def main_dgrad_add(windows=9, l3_bytes=256 << 20):
         tot["a"], tot["b"], tot["c"]))
 
 
+def _bottleneck_1x1_shapes(batch, stem_c, planes, depths, width_of):
+    """Distinct 1x1 GEMMs of a bottleneck net's forward at 224 px, as
+    {(M, N, K, residual, relu): count}: per block the reduce conv (ReLU), the
+    expand conv (+ shortcut, ReLU) and, in a stage's first block, the
+    projection shortcut (plain BN). The stride sits on the 3x3, so a first
+    block's reduce conv still runs at the previous stage's extent."""
+    out = {}
+
+    def add(*key):
+        out[key] = out.get(key, 0) + 1
+
+    cin, hw = stem_c, 56
+    for si, (p, d) in enumerate(zip(planes, depths)):
+        hw_in, hw = hw, hw if si == 0 else hw // 2
+        w, cout = width_of(p), 4 * p
+        for i in range(d):
+            m_in = batch * (hw_in if i == 0 else hw) ** 2
+            m = batch * hw * hw
+            add(m_in, w, cin, False, True)
+            add(m, cout, w, True, True)
+            if i == 0:
+                add(m, cout, cin, False, False)
+            cin = cout
+    return out
+
+
+def main_eval_bn(windows=9, l3_bytes=256 << 20):
+    """conv1x1 -> eval BN(+Add)+ReLU per shape, with and without a residual:
+    (a) gemm_bt + bn_fwd_eval (two launches), (b) gemm_bt_bn, (c) gemm_bt
+    alone. Cold operands and timing as --dgrad-add. `x` is how often the
+    forward runs that form (0: the other form of a shape, timed for
+    comparison, not in the totals). `fused` is what ops.conv.conv_bn does
+    with the shape by default: BNs wider than 2048 keep their own launch."""
+    e = ops.ext()
+    nets = [
+        ("ResNeXt101_32x16d bs16", _bottleneck_1x1_shapes(
+            16, 64, (64, 128, 256, 512), (3, 4, 23, 3), lambda p: 8 * p)),
+        ("ResNet50_vd bs32", _bottleneck_1x1_shapes(
+            32, 64, (64, 128, 256, 512), (3, 4, 6, 3), lambda p: p)),
+    ]
+    for name, shapes in nets:
+        for M, N, K, res, relu in list(shapes):
+            if not any(k[:4] == (M, N, K, not res) for k in shapes):
+                shapes[(M, N, K, not res, relu)] = 0
+        print(name)
+        print("%-22s %3s %3s %4s %-24s %-24s %-24s %s" % (
+            "shape (M,N,K)", "res", "act", "x", "(a) bt + bn_apply",
+            "(b) bt_bn", "(c) bt alone", "fused"))
+        tot = {"a": 0.0, "b": 0.0, "c": 0.0}
+        for (M, N, K, res, relu), cnt in sorted(
+                shapes.items(), key=lambda kv: (-kv[0][0], kv[0][1:])):
+            set_bytes = 2 * (M * K + N * K + (3 if res else 2) * M * N)
+            nsets = max(2, -(-int(1.25 * l3_bytes) // set_bytes))
+            sets = [(torch.randn(M, K, device="cuda").to(torch.bfloat16),
+                     torch.randn(N, K, device="cuda").to(torch.bfloat16),
+                     torch.randn(M, N, device="cuda").to(torch.bfloat16)
+                     if res else None,
+                     torch.randn(N, device="cuda"),
+                     torch.randn(N, device="cuda"))
+                    for _ in range(nsets)]
+            fns = {
+                "a": lambda a, b, r, sc, sh: e.bn_fwd_eval(
+                    e.gemm_bt(a, b), sc, sh, r, relu),
+                "b": lambda a, b, r, sc, sh: e.gemm_bt_bn(
+                    a, b, sc, sh, relu, r),
+                "c": lambda a, b, r, sc, sh: e.gemm_bt(a, b),
+            }
+            cols = []
+            for key in ("a", "b", "c"):
+                us = _graph_us(fns[key], sets, windows)
+                med = us[len(us) // 2]
+                tot[key] += med * cnt
+                cols.append("%7.1f [%6.1f..%6.1f]" % (med, us[0], us[-1]))
+            print("%-22s %3s %3s %4d %-24s %-24s %-24s %s" % (
+                str((M, N, K)), "+R" if res else "-", "y" if relu else "n",
+                cnt, *cols, "yes" if N <= 2048 else "no (wide BN)"),
+                flush=True)
+            del sets
+            torch.cuda.empty_cache()
+        print("per forward (x counts): (a) %.1f us  (b) %.1f us  (c) %.1f us"
+              % (tot["a"], tot["b"], tot["c"]))
+
+
 if __name__ == "__main__":
     if "--dgrad-add" in sys.argv:
         main_dgrad_add()
+    elif "--eval-bn" in sys.argv:
+        main_eval_bn()
     elif "--wgrad" in sys.argv:
         main_wgrad()
     elif "--wgrad3" in sys.argv:
