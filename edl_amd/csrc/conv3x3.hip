@@ -583,19 +583,28 @@ extern "C" void launch_conv3x3_small(const void* xp, const void* w3s, void* y,
 // igemm_bwd path replaced — VERDICT r1 #4). Weights come repacked as
 // wcat [Cin, 9*Cout], classes' tap slabs contiguous (conv.py
 // _repack_w3_s2dgrad), col_base selecting the class.
-template <int BM, int BN, int WAVES_M, int WAVES_N>
+// GROUPED (BN = 64, as the grouped forward): an input channel receives
+// gradient only from the output channels of its own group, so the 64-wide
+// n-tile at n0 reduces over the gw-channel dY window at (n0/gw)*gw and
+// nothing else: K = T*gw per class, B = wcat_g [C, 9*gw] (conv.py
+// _repack_w3_s2dgrad_grouped: per group transposed, block-diagonal for
+// cpg 16/32). Cout stays the dY row stride (all channels).
+template <int BM, int BN, int WAVES_M, int WAVES_N, bool GROUPED = false>
 __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(
     const bf16* __restrict__ DYP, const bf16* __restrict__ B,
     bf16* __restrict__ DX, const int M, const int N, const int Cout,
     const int Wc, const int HWc, const int Hop, const int Wop, const int H,
     const int W, const int ph, const int pw, const int T, const int col_base,
-    const int sh0, const int sh1, const int sh2, const int sh3) {
+    const int sh0, const int sh1, const int sh2, const int sh3,
+    const int gw = 0) {
+  static_assert(!GROUPED || BN == 64, "grouped dgrad: 64-wide n-tiles");
   constexpr int BK = 64;
   constexpr int A_BYTES = BM * BK * 2;
   constexpr int B_BYTES = BN * BK * 2;
-  const int K = T * Cout;       // this class's gemm K
-  const int Krow = 9 * Cout;    // B row stride (all classes)
-  const int cb_per_t = Cout >> 6;
+  const int Ck = GROUPED ? gw : Cout;  // dY channels entering the gemm K
+  const int K = T * Ck;         // this class's gemm K
+  const int Krow = 9 * Ck;      // B row stride (all classes)
+  const int cb_per_t = Ck >> 6;
   char* lds = smem;
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -623,6 +632,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(
     arow[i] = (((long long)n_img * Hop + i_r) * Wop + j_c) * Cout;
   }
   const int shift_elems[4] = {sh0, sh1, sh2, sh3};
+  const int a_ch_base = GROUPED ? (n0 / gw) * gw : 0;  // dY window base
 
   auto stage = [&](int buf, int kt) {
     const int s = kt / cb_per_t;
@@ -634,7 +644,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(
       const int ch = wave * (A_CHUNKS / 4) + i;
       const int r = ch * 8 + (lane >> 3);
       const int gslot = (lane & 7) ^ (r & 7);
-      const bf16* src = DYP + arow[i] + shift_elems[s] + cb * 64 + gslot * 8;
+      const bf16* src = DYP + arow[i] + shift_elems[s] + a_ch_base + cb * 64 +
+                        gslot * 8;
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void*)src,
           (__attribute__((address_space(3))) void*)(abase + ch * 1024), 16, 0, 0);
@@ -714,17 +725,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3s2_dgrad_kernel(
   }
 }
 
-extern "C" void launch_conv3x3s2_dgrad(const void* dyp, const void* wcat,
-                                       void* dx, int Nimg, int H, int W,
-                                       int Cin, int Cout, int Hop, int Wop,
-                                       hipStream_t s) {
-  // classes (ph,pw) with tap lists per the conv.py repack ordering
-  const int col_base[4] = {0, Cout, 3 * Cout, 5 * Cout};
+// The four parity classes (ph,pw) of the stride-2 dgrad, tap lists per the
+// conv.py repack ordering: launch(M, Hc, Wc, ph, pw, T, col_base, shifts)
+// once per non-empty class. Cout is the dY row stride (shifts are element
+// offsets into the padded dY), Ck the channels per tap slab of the weights
+// (Cout dense, gw grouped), which sets the class column bases.
+template <class F>
+static void s2_dgrad_classes(int Nimg, int H, int W, int Wop, int Cout, int Ck,
+                             F&& launch) {
+  const int col_base[4] = {0, Ck, 3 * Ck, 5 * Ck};
   const int dys[2][2] = {{1, 1}, {0, 2}};   // dys[ph][...]; ph=0 -> {1}
   const int ndy[2] = {1, 2};
   for (int ph = 0; ph < 2; ++ph) {
     for (int pw = 0; pw < 2; ++pw) {
-      const int cls = ph * 2 + pw;
       const int Hc = (H - ph + 1) / 2, Wc = (W - pw + 1) / 2;
       const int M = Nimg * Hc * Wc;
       if (M <= 0) continue;
@@ -736,7 +749,19 @@ extern "C" void launch_conv3x3s2_dgrad(const void* dyp, const void* wcat,
           const int r = (ph + 3 - dy) / 2, c = (pw + 3 - dxx) / 2;
           shifts[t++] = (r * Wop + c) * Cout;
         }
-      const int T = t;
+      launch(M, Hc, Wc, ph, pw, t, col_base[ph * 2 + pw], shifts);
+    }
+  }
+}
+
+extern "C" void launch_conv3x3s2_dgrad(const void* dyp, const void* wcat,
+                                       void* dx, int Nimg, int H, int W,
+                                       int Cin, int Cout, int Hop, int Wop,
+                                       hipStream_t s) {
+  s2_dgrad_classes(
+      Nimg, H, W, Wop, Cout, Cout,
+      [&](int M, int Hc, int Wc, int ph, int pw, int T, int col_base,
+          const int* shifts) {
       if (Cin % 128 == 0) {
         constexpr int BM = 128, BN = 128;
         const int grid = ((M + BM - 1) / BM) * (Cin / BN);
@@ -744,7 +769,7 @@ extern "C" void launch_conv3x3s2_dgrad(const void* dyp, const void* wcat,
         hipLaunchKernelGGL((conv3x3s2_dgrad_kernel<BM, BN, 2, 2>), dim3(grid),
                            dim3(256), lds_bytes, s, (const bf16*)dyp,
                            (const bf16*)wcat, (bf16*)dx, M, Cin, Cout, Wc,
-                           Hc * Wc, Hop, Wop, H, W, ph, pw, T, col_base[cls],
+                           Hc * Wc, Hop, Wop, H, W, ph, pw, T, col_base,
                            shifts[0], shifts[1], shifts[2], shifts[3]);
       } else {
         constexpr int BM = 256, BN = 64;
@@ -753,11 +778,32 @@ extern "C" void launch_conv3x3s2_dgrad(const void* dyp, const void* wcat,
         hipLaunchKernelGGL((conv3x3s2_dgrad_kernel<BM, BN, 4, 1>), dim3(grid),
                            dim3(256), lds_bytes, s, (const bf16*)dyp,
                            (const bf16*)wcat, (bf16*)dx, M, Cin, Cout, Wc,
-                           Hc * Wc, Hop, Wop, H, W, ph, pw, T, col_base[cls],
+                           Hc * Wc, Hop, Wop, H, W, ph, pw, T, col_base,
                            shifts[0], shifts[1], shifts[2], shifts[3]);
       }
-    }
-  }
+      });
+}
+
+// grouped twin (Cin == Cout == C): wcat_g [C, 9*gw], 64-wide n-tiles
+extern "C" void launch_conv3x3s2_dgrad_grouped(const void* dyp,
+                                               const void* wcat_g, void* dx,
+                                               int Nimg, int H, int W, int C,
+                                               int gw, int Hop, int Wop,
+                                               hipStream_t s) {
+  s2_dgrad_classes(
+      Nimg, H, W, Wop, C, gw,
+      [&](int M, int Hc, int Wc, int ph, int pw, int T, int col_base,
+          const int* shifts) {
+        constexpr int BM = 256, BN = 64;
+        const int grid = ((M + BM - 1) / BM) * (C / BN);
+        const int lds_bytes = 2 * (BM * 64 * 2 + BN * 64 * 2);
+        hipLaunchKernelGGL((conv3x3s2_dgrad_kernel<BM, BN, 4, 1, true>),
+                           dim3(grid), dim3(256), lds_bytes, s,
+                           (const bf16*)dyp, (const bf16*)wcat_g, (bf16*)dx, M,
+                           C, C, Wc, Hc * Wc, Hop, Wop, H, W, ph, pw, T,
+                           col_base, shifts[0], shifts[1], shifts[2],
+                           shifts[3], gw);
+      });
 }
 
 extern "C" void launch_pad_nhwc(const void* x, void* xp, int Nimg, int H, int W,

@@ -78,13 +78,27 @@ __device__ __forceinline__ int tn_swz(int r) {
 // staged k-tiles stay in flight across barriers (the __syncthreads form
 // drains every glds per iteration — guide 'pipelining across barriers';
 // costs 96 KB LDS -> 1 block/CU).
+// GRP (G3 only): grouped-conv wgrad. The output is dW3g [N1, 9*gw] (gw =
+// the gemm group width of conv3x3.hip's GROUPED mode; N2 = 9*gw), the
+// layout conv.py _repack_w3_grouped gives the forward. An N1 tile at t1
+// pairs ONLY with the 9*gw/BN2 column tiles of its own channel window
+// [(t1/gw)*gw, +gw) of xpad: column tile t2 is tap t2/gw at channel base
+// (t1/gw)*gw + t2%gw. BN1 <= gw and BN2 | gw keep a tile inside one window
+// and one tap; the xpad row stride stays Cin (all channels). Everything
+// past the two block-uniform gather parameters is the dense G3 kernel.
 template <int BN1, int BN2, int KW, bool G3 = false, bool TR = false,
-          bool DEEP = false, bool G3S = false, bool APAD = false>
+          bool DEEP = false, bool G3S = false, bool APAD = false,
+          bool GRP = false>
 __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
     const bf16* __restrict__ A, const bf16* __restrict__ B,
     float* __restrict__ C, const int N1, const int N2, const int K,
     const int Ho = 0, const int Wo = 0, const int Hp = 0, const int Wp = 0,
     const int Cin = 0, const int stride = 1, const int perm_cin = 0) {
+  static_assert(!GRP || (G3 && !G3S), "GRP is a G3 mode");
+  // GRP: gw arrives in the perm_cin slot (the grouped route has no
+  // direct-grad remap). One more kernel argument would move the hidden
+  // argument block, and with it the code of every other instantiation.
+  const int gw = GRP ? perm_cin : 0;
   constexpr int BK = 64;
   constexpr int W1 = BN1 / 64, W2 = BN2 / 64;  // wave sub-tiles per dim
   constexpr int GW = W1 * W2;                  // waves per k-group
@@ -119,7 +133,12 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
 
   // G3 block-uniform gather parameters (one 3x3 shift per col tile)
   int g3_sy = 0, g3_sx = 0, g3_ci0 = 0;
-  if constexpr (G3) {
+  if constexpr (GRP) {
+    const int sidx = t2 / gw;
+    g3_sy = sidx / 3;
+    g3_sx = sidx % 3;
+    g3_ci0 = (t1 / gw) * gw + t2 % gw;
+  } else if constexpr (G3) {
     const int sidx = t2 / Cin;
     g3_sy = sidx / 3;
     g3_sx = sidx % 3;
@@ -455,7 +474,7 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_kernel(
     for (int reg = 0; reg < 4; ++reg) {
       const int n1 = t1 + wm + mf * 16 + r4 + reg;
       if (n1 < N1) {
-        if (perm_cin > 0) {
+        if (!GRP && perm_cin > 0) {
           // direct-grad layout: C is the conv weight [Cout, Cin, 3, 3];
           // our n2 = s*Cin + ci (s-major) -> offset (n1*Cin + ci)*9 + s
 #pragma unroll
@@ -607,6 +626,42 @@ extern "C" void launch_gemm_tn3x3_splitk_apad(const void* dyp,
     tn3_apad_launch<64, 64, 4, false>(APAD_ARGS);
   }
 #undef APAD_ARGS
+}
+
+extern "C" void launch_gemm_tn3x3_grouped_splitk(const void* dy,
+                                                 const void* xpad, float* C,
+                                                 int Cch, int gw, int M,
+                                                 int Ho, int Wo, int Hp,
+                                                 int Wp, int stride,
+                                                 int splitk, hipStream_t s) {
+  // grouped wgrad dW3g[Cch, 9*gw] (GRP): gw 128 -> 128x128 tiles, KW 1,
+  // transposing LDS reads; gw 64 -> the dense path's 64x64 KW 4 pick.
+  // Wider gw (a multiple of 64 the forward never produces) takes 64x64.
+  const int N2 = 9 * gw;
+  if (gw % 128 == 0) {
+    const dim3 grid((Cch / 128) * (N2 / 128), splitk);
+    const int lds = 2 * (64 * 128 * 2 + 64 * 128 * 2);
+    if (tn_use_tr())
+      hipLaunchKernelGGL((gemm_tn_kernel<128, 128, 1, true, true, false, false,
+                                         false, true>),
+                         grid, dim3(256), lds, s, (const bf16*)dy,
+                         (const bf16*)xpad, C, Cch, N2, M, Ho, Wo, Hp, Wp, Cch,
+                         stride, gw);
+    else
+      hipLaunchKernelGGL((gemm_tn_kernel<128, 128, 1, true, false, false,
+                                         false, false, true>),
+                         grid, dim3(256), lds, s, (const bf16*)dy,
+                         (const bf16*)xpad, C, Cch, N2, M, Ho, Wo, Hp, Wp, Cch,
+                         stride, gw);
+  } else {
+    const dim3 grid((Cch / 64) * (N2 / 64), splitk);
+    const int lds = 4 * 2 * (64 * 64 * 2 + 64 * 64 * 2);
+    hipLaunchKernelGGL((gemm_tn_kernel<64, 64, 4, true, false, false, false,
+                                       false, true>),
+                       grid, dim3(256), lds, s, (const bf16*)dy,
+                       (const bf16*)xpad, C, Cch, N2, M, Ho, Wo, Hp, Wp, Cch,
+                       stride, gw);
+  }
 }
 
 extern "C" void launch_gemm_tn3x3_small(const void* dy, const void* xpad,

@@ -219,6 +219,10 @@ void launch_conv3x3_small(const void* xp, const void* w3s, void* y, int M,
 void launch_conv3x3s2_dgrad(const void* dyp, const void* wcat, void* dx,
                             int Nimg, int H, int W, int Cin, int Cout,
                             int Hop, int Wop, hipStream_t s);
+// grouped twin: one channel count C, wcat_g [C, 9*gw]
+void launch_conv3x3s2_dgrad_grouped(const void* dyp, const void* wcat_g,
+                                    void* dx, int Nimg, int H, int W, int C,
+                                    int gw, int Hop, int Wop, hipStream_t s);
 
 // ---- gemm_tn.hip ---- (3x3: Cout, Cin, M, then Ho, Wo, Hp, Wp; the small
 // launcher puts CinP BEFORE stride, the others end stride, splitk, perm)
@@ -232,6 +236,11 @@ void launch_gemm_tn3x3_splitk_apad(const void* dyp, const void* xpad,
                                    float* C, int Cout, int Cin, int M, int Ho,
                                    int Wo, int Hp, int Wp, int stride,
                                    int splitk, int perm, hipStream_t s);
+// grouped wgrad: C is dW3g [Cch, 9*gw]; Cch, gw stand where Cout, Cin do
+void launch_gemm_tn3x3_grouped_splitk(const void* dy, const void* xpad,
+                                      float* C, int Cch, int gw, int M, int Ho,
+                                      int Wo, int Hp, int Wp, int stride,
+                                      int splitk, hipStream_t s);
 void launch_gemm_tn3x3_small(const void* dy, const void* xpad, float* C,
                              int N1v, int N2v, int M, int Ho, int Wo, int Hp,
                              int Wp, int CinP, int stride, int splitk,

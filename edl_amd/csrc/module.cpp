@@ -1100,17 +1100,27 @@ torch::Tensor pad_nhwc_flat(const torch::Tensor& x, int cpad, hipStream_t s) {
   return xp;
 }
 
+torch::Tensor pad_nhwc(torch::Tensor x);  // padded-buffer section below
+void check_padded(const torch::Tensor& xp, int64_t H, int64_t W,
+                  const char* who);
+
 // scale/shift given: the eval BN(+ReLU) apply rides in the kernel epilogue
-torch::Tensor conv3x3_grouped_impl(const torch::Tensor& x,
+torch::Tensor conv3x3_grouped_impl(const torch::Tensor& xp,
                                    const torch::Tensor& w3g, int64_t stride,
+                                   int64_t H64, int64_t W64,
                                    const torch::Tensor* scale,
                                    const torch::Tensor* shift, bool relu) {
-  // grouped 3x3: w3g [Cout, 9*gw] where gw = the gemm group width —
-  // channels-per-group when >= 64 (exact, zero wasted MFMA), else 64
-  // with a block-diagonal zero-padded repack (conv.py _repack_w3_grouped)
-  check_nhwc_bf16(x, "conv3x3g");
-  const int Nimg = (int)x.size(0), Cin = (int)x.size(1);
-  const int H = (int)x.size(2), W = (int)x.size(3);
+  // grouped 3x3 on the zero-halo padded input xp [N, H+2, W+2, Cin]: w3g
+  // [Cout, 9*gw] where gw = the gemm group width — channels-per-group
+  // when >= 64 (exact, zero wasted MFMA), else 64 with a block-diagonal
+  // zero-padded repack (conv.py _repack_w3_grouped)
+  check_padded(xp, H64, W64, "conv3x3g");
+  TORCH_CHECK(stride == 1 || stride == 2, "conv3x3g: stride 1 or 2");
+  const int Nimg = (int)xp.size(0), Cin = (int)xp.size(3);
+  const int H = (int)H64, W = (int)W64;
+  TORCH_CHECK(w3g.is_cuda() && w3g.device() == xp.device() &&
+                  w3g.scalar_type() == torch::kBFloat16 && w3g.dim() == 2,
+              "conv3x3g: w3g 2-D bf16 on the input's device");
   const int Cout = (int)w3g.size(0);
   TORCH_CHECK(w3g.size(1) % 9 == 0 && w3g.is_contiguous(), "conv3x3g: w3g");
   const int gw = (int)(w3g.size(1) / 9);
@@ -1118,12 +1128,11 @@ torch::Tensor conv3x3_grouped_impl(const torch::Tensor& x,
   TORCH_CHECK(Cin % 64 == 0 && Cout % 64 == 0 && Cin == Cout,
               "conv3x3g: C % 64, equal in/out");
   if (scale != nullptr)
-    check_bn_affine(*scale, *shift, Cout, x, "conv3x3g_bn");
+    check_bn_affine(*scale, *shift, Cout, xp, "conv3x3g_bn");
   const int Hout = out_extent(H, stride), Wout = out_extent(W, stride);
   const long long M = (long long)Nimg * Hout * Wout;
   auto s = cur_stream();
-  auto xp = pad_nhwc_flat(x, Cin, s);
-  auto y = torch::empty({M, Cout}, x.options());
+  auto y = torch::empty({M, Cout}, xp.options());
   if (scale != nullptr)
     launch_conv3x3_grouped_bn(xp.data_ptr(), w3g.data_ptr(), y.data_ptr(),
                               (int)M, Cout, Cin, Hout * Wout, Wout, H + 2,
@@ -1136,15 +1145,27 @@ torch::Tensor conv3x3_grouped_impl(const torch::Tensor& x,
   return y;
 }
 
+// xp already padded (the training forward pads once and keeps xp for the
+// wgrad); the unsuffixed entry points pad and forward
+torch::Tensor conv3x3_grouped_fwd_padded(torch::Tensor xp, torch::Tensor w3g,
+                                         int64_t stride, int64_t H,
+                                         int64_t W) {
+  return conv3x3_grouped_impl(xp, w3g, stride, H, W, nullptr, nullptr, false);
+}
+
 torch::Tensor conv3x3_grouped_fwd(torch::Tensor x, torch::Tensor w3g,
                                   int64_t stride) {
-  return conv3x3_grouped_impl(x, w3g, stride, nullptr, nullptr, false);
+  check_nhwc_bf16(x, "conv3x3g");
+  return conv3x3_grouped_impl(pad_nhwc(x), w3g, stride, x.size(2), x.size(3),
+                              nullptr, nullptr, false);
 }
 
 torch::Tensor conv3x3_grouped_fwd_bn(torch::Tensor x, torch::Tensor w3g,
                                      int64_t stride, torch::Tensor scale,
                                      torch::Tensor shift, bool relu) {
-  return conv3x3_grouped_impl(x, w3g, stride, &scale, &shift, relu);
+  check_nhwc_bf16(x, "conv3x3g");
+  return conv3x3_grouped_impl(pad_nhwc(x), w3g, stride, x.size(2), x.size(3),
+                              &scale, &shift, relu);
 }
 
 // stem conv (small channels): x [N, Cin, H, W] channels_last bf16 with
@@ -1250,6 +1271,39 @@ torch::Tensor conv3x3s2_dgrad(torch::Tensor dy, torch::Tensor wcat,
   TORCH_CHECK((H + 1) / 2 == dy.size(2) && (W + 1) / 2 == dy.size(3),
               "s2dgrad: shape");
   return conv3x3s2_dgrad_padded(pad_nhwc(dy), wcat, H, W);
+}
+
+torch::Tensor conv3x3s2_dgrad_grouped_padded(torch::Tensor dyp,
+                                             torch::Tensor wcat_g, int64_t H,
+                                             int64_t W) {
+  // grouped stride-2 dgrad. dyp: zero-halo padded dY [N, Ho+2, Wo+2, C];
+  // wcat_g: [C, 9*gw] (conv.py _repack_w3_s2dgrad_grouped), gw the gemm
+  // group width of the grouped forward. Returns dx2d [N*H*W, C] bf16.
+  const int64_t Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  check_padded(dyp, Ho, Wo, "s2dgrad_g");
+  const int Nimg = (int)dyp.size(0), C = (int)dyp.size(3);
+  TORCH_CHECK(wcat_g.is_cuda() && wcat_g.device() == dyp.device() &&
+                  wcat_g.scalar_type() == torch::kBFloat16 &&
+                  wcat_g.dim() == 2 && wcat_g.is_contiguous() &&
+                  wcat_g.size(0) == C && wcat_g.size(1) % 9 == 0,
+              "s2dgrad_g: wcat_g contiguous bf16 [C, 9*gw] on dy's device");
+  const int gw = (int)(wcat_g.size(1) / 9);
+  TORCH_CHECK(gw > 0 && gw % 64 == 0 && C % gw == 0,
+              "s2dgrad_g: gw % 64, C % gw");
+  auto dx = torch::empty({(long long)Nimg * H * W, C}, dyp.options());
+  launch_conv3x3s2_dgrad_grouped(dyp.data_ptr(), wcat_g.data_ptr(),
+                                 dx.data_ptr(), Nimg, (int)H, (int)W, C, gw,
+                                 (int)Ho + 2, (int)Wo + 2, cur_stream());
+  return dx;
+}
+
+torch::Tensor conv3x3s2_dgrad_grouped(torch::Tensor dy, torch::Tensor wcat_g,
+                                      int64_t H, int64_t W) {
+  // dy: [N, C, Ho, Wo] channels_last bf16 (pads, then the call above)
+  check_nhwc_bf16(dy, "s2dgrad_g dy", 64);
+  TORCH_CHECK((H + 1) / 2 == dy.size(2) && (W + 1) / 2 == dy.size(3),
+              "s2dgrad_g: dy is not the stride-2 output of an H x W image");
+  return conv3x3s2_dgrad_grouped_padded(pad_nhwc(dy), wcat_g, H, W);
 }
 
 torch::Tensor repack_dgrad_w3(torch::Tensor w_smaj, int64_t ci,
@@ -1449,6 +1503,43 @@ torch::Tensor gemm_tn3x3_splitk(torch::Tensor dy2d, torch::Tensor x,
   auto xp = pad_nhwc(x);
   return gemm_tn3x3_splitk_padded(dy2d, xp, x.size(2), x.size(3), stride,
                                   splitk, out);
+}
+
+torch::Tensor gemm_tn3x3_grouped_splitk_padded(torch::Tensor dy2d,
+                                               torch::Tensor xp, int64_t H64,
+                                               int64_t W64, int64_t stride,
+                                               int64_t gw64, int64_t splitk) {
+  // grouped conv3x3 wgrad: fp32 dW3g[C, 9*gw] = per channel window, dY^T @
+  // gather3x3(xp) — the layout conv.py _repack_w3_grouped gives the
+  // forward (cpg 16/32: block-diagonal, the off-diagonal blocks hold the
+  // cross-group products and are dropped by _unpack_dw3_grouped).
+  // dy2d: [M, C] bf16 NHWC-flattened dY; xp: padded input [N, H+2, W+2, C].
+  check_padded(xp, H64, W64, "gemm_tn3x3g");
+  TORCH_CHECK(stride == 1 || stride == 2, "gemm_tn3x3g: stride 1 or 2");
+  TORCH_CHECK(dy2d.is_cuda() && dy2d.device() == xp.device() &&
+                  dy2d.dim() == 2 && dy2d.scalar_type() == torch::kBFloat16,
+              "gemm_tn3x3g: dy2d [M, C] bf16 on xp's device");
+  const int Nimg = (int)xp.size(0), C = (int)xp.size(3);
+  const int H = (int)H64, W = (int)W64, gw = (int)gw64;
+  const int Ho = out_extent(H, stride), Wo = out_extent(W, stride);
+  const int M = Nimg * Ho * Wo;
+  TORCH_CHECK(gw > 0 && gw % 64 == 0 && C % gw == 0,
+              "gemm_tn3x3g: gw % 64, C % gw");
+  TORCH_CHECK(M > 0 && dy2d.size(0) == M && dy2d.size(1) == C,
+              "gemm_tn3x3g: dy2d is not [N*Ho*Wo, C]");
+  auto dyc = dy2d.contiguous();
+  const int nchunks = (M + 63) / 64;
+  const int tile = gw % 128 == 0 ? 128 : 64;
+  if (splitk <= 0)
+    splitk = auto_splitk((C / tile) * (9 * gw / tile), nchunks);
+  splitk = std::min<int64_t>(splitk, nchunks);
+  auto c = torch::zeros({C, (long long)9 * gw},
+                        xp.options().dtype(torch::kFloat32));
+  launch_gemm_tn3x3_grouped_splitk(dyc.data_ptr(), xp.data_ptr(),
+                                   c.data_ptr<float>(), C, gw, M, Ho, Wo,
+                                   H + 2, W + 2, (int)stride, (int)splitk,
+                                   cur_stream());
+  return c;
 }
 
 torch::Tensor transpose_pad(torch::Tensor x) {
@@ -1796,6 +1887,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "gemm_tn3x3_splitk on padded xp; dy [M,Cout] or padded 4-D",
         py::arg("dy"), py::arg("xp"), py::arg("H"), py::arg("W"),
         py::arg("stride"), py::arg("splitk") = 0, py::arg("out") = py::none());
+  m.def("conv3x3_grouped_fwd_padded", &conv3x3_grouped_fwd_padded,
+        "conv3x3_grouped_fwd on an already padded xp [N,H+2,W+2,C]",
+        py::arg("xp"), py::arg("w3g"), py::arg("stride"), py::arg("H"),
+        py::arg("W"));
+  m.def("conv3x3s2_dgrad_grouped", &conv3x3s2_dgrad_grouped,
+        "grouped stride-2 3x3 dgrad: (dy, wcat_g [C,9*gw], H, W) -> dx2d",
+        py::arg("dy"), py::arg("wcat_g"), py::arg("H"), py::arg("W"));
+  m.def("gemm_tn3x3_grouped_splitk_padded", &gemm_tn3x3_grouped_splitk_padded,
+        "grouped conv3x3 wgrad: fp32 dW3g[C,9*gw] from dy2d [M,C] and padded "
+        "xp, per gw-channel window",
+        py::arg("dy2d"), py::arg("xp"), py::arg("H"), py::arg("W"),
+        py::arg("stride"), py::arg("gw"), py::arg("splitk") = 0);
   m.def("conv3x3_wgrad_operand_padded", &conv3x3_wgrad_operand_padded,
         "conv3x3_wgrad_operand on an already padded xp", py::arg("xp"),
         py::arg("H"), py::arg("W"), py::arg("stride"));

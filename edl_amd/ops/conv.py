@@ -5,8 +5,8 @@ y[M, Cout] = x[M, Cin] @ W^T — routed through torch.matmul (hipBLASLt on
 ROCm), which runs far closer to the MFMA roofline than MIOpen's igemm
 path at these shapes (igemm measured ~2-4% of bf16 peak at bs32, by
 rocprof). 3x3 same-pad convolutions run the in-repo implicit-GEMM kernels
-(dense C % 64, small-channel stem, grouped inference); everything else
-stays on F.conv2d (MIOpen).
+(dense C % 64, small-channel stem, grouped ResNeXt shapes — forward and
+backward); everything else stays on F.conv2d (MIOpen).
 
 Weight layout stays nn.Conv2d-compatible ([Cout, Cin, kh, kw]) so state
 dicts interchange."""
@@ -121,12 +121,17 @@ class _Conv1x1Hip(torch.autograd.Function):
 _CONV3X3 = os.environ.get("EDL_CONV3X3", "hip")
 
 # Grouped-conv routing: groups with >= this many channels-per-group run
-# the in-repo grouped kernel (teacher fwd); below it, MIOpen. Measured
+# the in-repo grouped kernels (fwd, and dgrad/wgrad when a gradient is
+# wanted — see EDL_CONV3X3_GROUPED_TRAIN); below it, MIOpen. Measured
 # r2 (gpurun_out/r2c3/teacher_fwd_b16.log): routing EVERYTHING (16) wins
 # — ResNeXt101 teacher fwd 13.4 -> 5.5 ms/bs16 (2.4x vs all-MIOpen);
 # even the 4x-zero cpg=16 block-diagonal beats MIOpen once the rest of
 # the net runs in-repo kernels.
 _GROUPED_MINC = int(os.environ.get("EDL_CONV3X3_GROUPED_MINC", "16"))
+# A grouped 3x3 that needs a gradient (teacher fine-tune, ResNeXt student)
+# runs _Conv3x3GroupedHip: forward, dgrad and wgrad on the in-repo kernels.
+# 0 = nn.Conv2d (MIOpen) for all three passes, as before.
+_GROUPED_TRAIN = os.environ.get("EDL_CONV3X3_GROUPED_TRAIN", "1") == "1"
 
 # Fold BN stats partials into the conv fwd epilogues (the following BN
 # skips its stats kernel — a full activation re-read, ~0.53 ms/step).
@@ -456,6 +461,100 @@ def _repack_w3_grouped(weight):
     return out.reshape(co, 9 * 64).contiguous()
 
 
+def _group_transposed(weight):
+    """Grouped [C, cpg, 3, 3] with the in/out channel roles swapped inside
+    every group: w_t[g*cpg + ci, co] = w[g*cpg + co, ci] (taps untouched) —
+    the weight of the dgrad seen as a grouped conv over dy."""
+    c, cpg = weight.shape[0], weight.shape[1]
+    w = weight.detach().reshape(c // cpg, cpg, cpg, 3, 3)
+    return w.transpose(1, 2).reshape(c, cpg, 3, 3)
+
+
+def _repack_w3_grouped_rot(weight):
+    """Stride-1 grouped dgrad weights: dx = conv3x3_grouped_fwd(dy, this, 1)
+    — per group transposed, taps rotated 180 degrees, then the forward's
+    own repack."""
+    return _repack_w3_grouped(_group_transposed(weight).flip(2, 3))
+
+
+def _repack_w3_s2dgrad_grouped(weight):
+    """[C, cpg, 3, 3] -> wcat_g [C, 9*gw] bf16 for the grouped stride-2
+    dgrad (conv3x3.hip conv3x3s2_dgrad_kernel GROUPED): row = INPUT channel,
+    columns = the parity classes' tap slabs in _S2D_TAP_ORDER (bases
+    [0, gw, 3gw, 5gw]), each slab the gw output channels of the row's
+    channel window — block-diagonal zero-padded for cpg 16/32 exactly as
+    _repack_w3_grouped."""
+    w3g = _repack_w3_grouped(_group_transposed(weight))  # [C, 9*gw] s-major
+    c = w3g.shape[0]
+    taps = torch.tensor([dy * 3 + dx for dy, dx in _S2D_TAP_ORDER],
+                        device=w3g.device)
+    return w3g.view(c, 9, -1).index_select(1, taps).reshape(c, -1).contiguous()
+
+
+def _unpack_dw3_grouped(dw3g, cpg):
+    """dW3g [C, 9*gw] (the grouped wgrad kernel's output, the layout of
+    _repack_w3_grouped) -> [C, cpg, 3, 3]. cpg >= 64: a view-permute.
+    cpg 16/32: out-channel n's cpg real columns are the diagonal block at
+    ((n // cpg) % (64 // cpg)) * cpg; the rest (cross-group products) is
+    dropped."""
+    c = dw3g.shape[0]
+    v = dw3g.view(c, 3, 3, -1)
+    if cpg < 64:
+        base = (torch.arange(c, device=v.device) // cpg) % (64 // cpg) * cpg
+        cols = base[:, None] + torch.arange(cpg, device=v.device)
+        v = v.gather(3, cols[:, None, None, :].expand(c, 3, 3, cpg))
+    return v.permute(0, 3, 1, 2)
+
+
+class _Conv3x3GroupedHip(torch.autograd.Function):
+    """Grouped 3x3 same-pad conv (Conv2dFast._is_grouped3x3 shapes) with
+    every pass in-repo: forward on the GROUPED implicit-GEMM kernel; dgrad
+    the same kernel on per-group rotated weights (stride 1) or the GROUPED
+    parity kernel (stride 2); wgrad the GRP gather kernel of gemm_tn.hip,
+    written in the forward's [C, 9*gw] layout and unpacked here."""
+
+    @staticmethod
+    def forward(ctx, x, w_param, w3g, wd, stride):
+        # wd: stride 1 the rotated repack, stride 2 wcat_g; None when x
+        # needs no gradient. The input is padded ONCE: the padded buffer is
+        # what the wgrad reads, so it is saved in place of x.
+        e = ext()
+        n, c, h, w = x.shape
+        xp = e.pad_nhwc(x)
+        if w_param.requires_grad:
+            ctx.save_for_backward(xp if _PAD_ONCE else x)
+        ctx.x_shape = (n, c, h, w)
+        ctx.stride = stride
+        ctx.wd = wd
+        ctx.cpg = w_param.shape[1]
+        ctx.w_dtype = w_param.dtype
+        y2d = e.conv3x3_grouped_fwd_padded(xp, w3g, stride, h, w)
+        return _nchw_view(y2d, n, *_out_hw(h, w, stride))
+
+    @staticmethod
+    def backward(ctx, dy):
+        e = ext()
+        n, c, h, w = ctx.x_shape
+        stride = ctx.stride
+        dy = dy.contiguous(memory_format=torch.channels_last).to(
+            torch.bfloat16)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            if stride == 1:
+                dx2d = e.conv3x3_grouped_fwd(dy, ctx.wd, 1)
+            else:
+                dx2d = e.conv3x3s2_dgrad_grouped(dy, ctx.wd, h, w)
+            dx = _nchw_view(dx2d, n, h, w)
+        if ctx.needs_input_grad[1]:
+            (xs,) = ctx.saved_tensors
+            xp = xs if _PAD_ONCE else e.pad_nhwc(xs)
+            dy2d = dy.permute(0, 2, 3, 1).reshape(-1, c)
+            dw3g = e.gemm_tn3x3_grouped_splitk_padded(
+                dy2d, xp, h, w, stride, max(ctx.cpg, 64), 0)
+            dw = _unpack_dw3_grouped(dw3g, ctx.cpg).to(ctx.w_dtype)
+        return dx, dw, None, None, None
+
+
 class Conv2dFast(nn.Conv2d):
     """nn.Conv2d drop-in; 1x1/group-1 convs on CUDA bypass MIOpen."""
 
@@ -624,11 +723,14 @@ class Conv2dFast(nn.Conv2d):
                     and os.environ.get("EDL_CONV3X3_SMALL", "1") == "1"
                     and self._is_small3x3()):
                 return self._forward_small3x3(x, bn_stats)
-            if (bf16 and self._is_grouped3x3()
-                    and not (torch.is_grad_enabled() and
-                             (x.requires_grad or self.weight.requires_grad))):
-                # grouped teacher convs: eval/inference-only fast path
-                return self._forward_grouped3x3(x)
+            if bf16 and self._is_grouped3x3():
+                if not (torch.is_grad_enabled() and
+                        (x.requires_grad or self.weight.requires_grad)):
+                    # nothing to differentiate (teacher serving, frozen
+                    # blocks): the bare forward kernel
+                    return self._forward_grouped3x3(x)
+                if _GROUPED_TRAIN:
+                    return self._forward_grouped3x3_train(x)
         if (
             _CONV1X1 != "miopen"
             and x.is_cuda
@@ -726,6 +828,22 @@ class Conv2dFast(nn.Conv2d):
         y2d = ext().conv3x3_grouped_fwd(x, w3g, self.stride[0])
         n, _, h, w = x.shape
         return _nchw_view(y2d, n, *_out_hw(h, w, self.stride[0]))
+
+    def _forward_grouped3x3_train(self, x):
+        # a gradient is wanted: forward, dgrad and wgrad all in-repo. No
+        # direct-grad mode and no fused BN stats on this route.
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        w3g = self._cached("w3g", lambda: _repack_w3_grouped(self.weight))
+        wd = None
+        if x.requires_grad and self.stride[0] == 1:
+            wd = self._cached(
+                "w3g_rot", lambda: _repack_w3_grouped_rot(self.weight))
+        elif x.requires_grad:
+            wd = self._cached(
+                "wcat_g", lambda: _repack_w3_s2dgrad_grouped(self.weight))
+        return _Conv3x3GroupedHip.apply(x, self.weight, w3g, wd,
+                                        self.stride[0])
 
     def _forward_1x1(self, x, bn_stats, fork=False):
         # fork (checked by forward: hip route, bf16, stride 1, x dense

@@ -3,6 +3,7 @@ conv1x1 shapes at bs32. Run on a GPU box:
     python tools/gemm_bench.py
     python tools/gemm_bench.py --dgrad-add   # fused residual-add dgrad
     python tools/gemm_bench.py --eval-bn     # conv1x1 + eval BN in one kernel
+    python tools/gemm_bench.py --grouped-bwd # grouped 3x3 dgrad/wgrad vs MIOpen
 """
 import os
 import sys
@@ -250,8 +251,72 @@ def main_eval_bn(windows=9, l3_bytes=256 << 20):
               % (tot["a"], tot["b"], tot["c"]))
 
 
+# (C, cpg, output extent) of the ResNeXt101_32x16d grouped 3x3s
+GROUPED_SHAPES = [(512, 16, 56), (1024, 32, 28), (2048, 64, 14),
+                  (4096, 128, 7)]
+
+
+def main_grouped_bwd(batch=16, windows=9, l3_bytes=256 << 20):
+    """Grouped 3x3 backward per shape and stride: dgrad and wgrad on the
+    in-repo kernels, exactly the calls _Conv3x3GroupedHip.backward makes
+    (dy pad included; wgrad with its unpack to [C, cpg, 3, 3] bf16), against
+    torch.nn.grad.conv2d_input / conv2d_weight on channels_last bf16 (the
+    MIOpen route of EDL_CONV3X3_GROUPED_TRAIN=0). The stride-2 form reads an
+    input of twice the extent. Cold operands and timing as --dgrad-add."""
+    from edl_amd.ops import conv as cv
+    e = ops.ext()
+    cl = torch.channels_last
+    print("%-20s %-5s %-24s %-24s %6s" % (
+        "(C,cpg,out,stride)", "pass", "in-repo us", "library us", "lib/hip"))
+    for C, cpg, ho in GROUPED_SHAPES:
+        for s in (1, 2):
+            h = ho * s
+            gw, groups = max(cpg, 64), C // cpg
+            w = (torch.randn(C, cpg, 3, 3, device="cuda") * 0.05).to(
+                torch.bfloat16).contiguous(memory_format=cl)
+            wd = (cv._repack_w3_grouped_rot(w) if s == 1
+                  else cv._repack_w3_s2dgrad_grouped(w))
+            set_bytes = 2 * batch * C * (2 * h * h + ho * ho)
+            nsets = max(2, -(-int(1.25 * l3_bytes) // set_bytes))
+            sets = []
+            for _ in range(nsets):
+                x = torch.randn(batch, C, h, h, device="cuda").to(
+                    torch.bfloat16).contiguous(memory_format=cl)
+                dy = torch.randn(batch, C, ho, ho, device="cuda").to(
+                    torch.bfloat16).contiguous(memory_format=cl)
+                sets.append((x, e.pad_nhwc(x), dy))
+            fns = {
+                ("dgrad", "hip"): (lambda x, xp, dy: e.conv3x3_grouped_fwd(
+                    dy, wd, 1)) if s == 1 else (
+                    lambda x, xp, dy: e.conv3x3s2_dgrad_grouped(dy, wd, h, h)),
+                ("dgrad", "lib"): lambda x, xp, dy: torch.nn.grad.conv2d_input(
+                    x.shape, w, dy, stride=s, padding=1, groups=groups),
+                ("wgrad", "hip"): lambda x, xp, dy: cv._unpack_dw3_grouped(
+                    e.gemm_tn3x3_grouped_splitk_padded(
+                        dy.permute(0, 2, 3, 1).reshape(-1, C), xp, h, h, s,
+                        gw, 0), cpg).to(torch.bfloat16),
+                ("wgrad", "lib"): lambda x, xp, dy:
+                    torch.nn.grad.conv2d_weight(
+                        x, w.shape, dy, stride=s, padding=1, groups=groups),
+            }
+            for p in ("dgrad", "wgrad"):
+                cols, med = [], {}
+                for r in ("hip", "lib"):
+                    us = _graph_us(fns[(p, r)], sets, windows)
+                    med[r] = us[len(us) // 2]
+                    cols.append("%8.1f [%7.1f..%7.1f]" % (
+                        med[r], us[0], us[-1]))
+                print("%-20s %-5s %-24s %-24s %5.2fx" % (
+                    str((C, cpg, ho, s)), p, *cols, med["lib"] / med["hip"]),
+                    flush=True)
+            del sets
+            torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
-    if "--dgrad-add" in sys.argv:
+    if "--grouped-bwd" in sys.argv:
+        main_grouped_bwd()
+    elif "--dgrad-add" in sys.argv:
         main_dgrad_add()
     elif "--eval-bn" in sys.argv:
         main_eval_bn()
