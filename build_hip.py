@@ -54,6 +54,14 @@ def build(verbose=True):
         "-Wno-deprecated-declarations", "-Wno-unused-result",
     ] + ["-I" + i for i in tp["includes"]] + ["-I" + CSRC]
 
+    # per-source extras. bn_finalize.hip: no packed-fp32 VALU ops (v_pk_add/
+    # mul/fma_f32) — the kernel is latency-bound, the packed forms buy
+    # nothing there, and its folds stay plain v_add_f32 chains.
+    extra_flags = {
+        "bn_finalize.hip": ["-Xclang", "-target-feature",
+                            "-Xclang", "-packed-fp32-ops"],
+    }
+
     objs = []
     # every source includes launchers.h (the checked ABI), the kernels
     # common.h too: any header change rebuilds every object
@@ -69,6 +77,7 @@ def build(verbose=True):
         objs.append(op)
         if newer([sp] + hdr, op):
             run([HIPCC, "-c", sp, "-o", op] + common_flags +
+                extra_flags.get(src, []) +
                 (["-x", "hip"] if src.endswith(".hip") else []))
 
     ext_suffix = sysconfig.get_config_var("EXT_SUFFIX") or ".so"

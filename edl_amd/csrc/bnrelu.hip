@@ -202,68 +202,8 @@ __global__ void bn_stats_kernel(
   fold_end(lsum, s, q, c0, C, blockDim.x, partial);
 }
 
-// K2: strip-parallel fwd finalize — reduce the partials over blocks,
-// finalize mean/invstd/scale/shift, update the running stats. 256 threads
-// = 64 channels x 4 strips over the block range (one thread per channel
-// ran a single wave at C=64, serially reading every partial:
-// latency-bound).
-extern "C" __global__ void bn_finalize_kernel(
-    float* __restrict__ partial, const int nblocks, const int zero_src,
-    const float* __restrict__ gamma,
-    const float* __restrict__ beta, float* __restrict__ mean_out,
-    float* __restrict__ invstd_out, float* __restrict__ scale_out,
-    float* __restrict__ shift_out, float* __restrict__ running_mean,
-    float* __restrict__ running_var, const float momentum, const float eps,
-    const long long M, const int C) {
-  __shared__ float accs[4][64];
-  __shared__ float accq[4][64];
-  const int lane = threadIdx.x & 63;
-  const int strip = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane;
-  const long long st = 2 * C;
-  float sa[4] = {0}, qa[4] = {0};
-  if (c < C) {
-    int b = strip;
-    for (; b + 12 < nblocks; b += 16) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const long long i0 = (long long)(b + 4 * u) * st + c;
-        sa[u] += partial[i0];
-        qa[u] += partial[i0 + C];
-        if (zero_src) { partial[i0] = 0.0f; partial[i0 + C] = 0.0f; }
-      }
-    }
-    for (; b < nblocks; b += 4) {
-      const long long i0 = (long long)b * st + c;
-      sa[0] += partial[i0];
-      qa[0] += partial[i0 + C];
-      if (zero_src) { partial[i0] = 0.0f; partial[i0 + C] = 0.0f; }
-    }
-  }
-  accs[strip][lane] = (sa[0] + sa[1]) + (sa[2] + sa[3]);
-  accq[strip][lane] = (qa[0] + qa[1]) + (qa[2] + qa[3]);
-  __syncthreads();
-  if (strip != 0 || c >= C) return;
-  const float s = (accs[0][lane] + accs[1][lane]) +
-                  (accs[2][lane] + accs[3][lane]);
-  const float q = (accq[0][lane] + accq[1][lane]) +
-                  (accq[2][lane] + accq[3][lane]);
-  const float inv_m = 1.0f / (float)M;
-  const float mean = s * inv_m;
-  const float var = fmaxf(q * inv_m - mean * mean, 0.0f);
-  const float invstd = rsqrtf(var + eps);
-  mean_out[c] = mean;
-  invstd_out[c] = invstd;
-  const float g = gamma[c];
-  scale_out[c] = g * invstd;
-  shift_out[c] = beta[c] - g * invstd * mean;
-  if (running_mean != nullptr) {
-    // unbiased variance for the running estimate (torch semantics)
-    const float ub = (M > 1) ? var * (float)M / (float)(M - 1) : var;
-    running_mean[c] = fmaf(momentum, mean - running_mean[c], running_mean[c]);
-    running_var[c] = fmaf(momentum, ub - running_var[c], running_var[c]);
-  }
-}
+// K2: the fwd finalize (partials -> mean/invstd/scale/shift, running stats)
+// lives in bn_finalize.hip.
 
 // One octet of the fwd apply: v = relu?(v*scale + shift [+ res]). Returns
 // the ReLU mask byte (bit k = channel c0+k positive), 0 without RELU.
@@ -708,9 +648,12 @@ static int bn_grid_common(long long M, int C, long long cap_env) {
 extern "C" int bn_stats_grid(long long M, int C) {
   // cover the tensor with enough blocks for bandwidth, but keep the
   // partial buffer (grid x 2C fp32) around <= 1 MiB.
-  // cap bounds the finalize kernels' serial partial-read loop (they were
-  // latency-bound at ~12-14 us with 512-block partials; ~5 us at 192).
-  // EDL_BN_GRID_CAP overrides for A/B (192 = measured best tradeoff).
+  // The fwd finalize (bn_finalize.hip) reads up to 192 rows in one batch
+  // of loads, so its cost no longer grows with the grid up to there; the
+  // bwd finalize still walks its rows 8 at a time (~4.7 us up to 192 rows,
+  // the dispatch floor). EDL_BN_GRID_CAP overrides for A/B; 192 stays:
+  // the bwd sweep still loses at 384 and 768
+  // (profiles/bn_finalize_trace_before_after.txt).
   return bn_grid_common(M, C, env_ll("EDL_BN_GRID_CAP", 192));
 }
 
@@ -744,19 +687,6 @@ extern "C" void launch_bn_stats(const void* x, float* partial, int grid,
                                 long long M, int C, hipStream_t s) {
   hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(256), 0, s,
                      (const bf16*)x, partial, M, C);
-}
-
-extern "C" void launch_bn_finalize(float* partial, int nblocks, int zero_src,
-                                   const float* gamma,
-                                   const float* beta, float* mean, float* invstd,
-                                   float* scale, float* shift, float* rmean,
-                                   float* rvar, float momentum, float eps,
-                                   long long M, int C, hipStream_t s) {
-  // zero_src: store 0 back after each read — returns a pooled pre_part
-  // buffer to the pool clean, killing the per-step FillFunctor launches
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, s,
-                     partial, nblocks, zero_src, gamma, beta, mean, invstd,
-                     scale, shift, rmean, rvar, momentum, eps, M, C);
 }
 
 extern "C" void launch_bn_bwd_finalize(const float* partial, int nblocks,
