@@ -57,9 +57,11 @@ def build(verbose=True):
     # per-source extras. bn_finalize.hip: no packed-fp32 VALU ops (v_pk_add/
     # mul/fma_f32) — the kernel is latency-bound, the packed forms buy
     # nothing there, and its folds stay plain v_add_f32 chains.
+    no_pk = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
     extra_flags = {
-        "bn_finalize.hip": ["-Xclang", "-target-feature",
-                            "-Xclang", "-packed-fp32-ops"],
+        "bn_finalize.hip": no_pk,
+        # head.hip: its fp32 VALU work is the LDS folds and a divide
+        "head.hip": no_pk,
     }
 
     objs = []

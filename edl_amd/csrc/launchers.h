@@ -270,6 +270,24 @@ void launch_avgpool2x2_fwd(const void* x, void* y, int N, int H, int W,
 void launch_avgpool2x2_bwd(const void* dy, void* dx, int N, int H, int W,
                            int Ho, int Wo, int C, hipStream_t s);
 
+// ---- head.hip ---- (global avg-pool + FC; N, HW, C, K in that order, K =
+// classes; x [N, HW, C], w [K, C], pooled [N, C], logits / dl [N, K] bf16)
+// Range the kernels are written for: C % 64 == 0, N*HW*C < 2^31, all
+// pointers 16-byte aligned except logits / dl rows (any K).
+constexpr int kHeadMaxRows = 512;  // batch rows
+constexpr int kHeadMaxC = 4096;
+// two launches: pool, then the skinny GEMM; bias fp32 [K] or null
+void launch_head_fwd(const void* x, const void* w, const float* bias,
+                     void* pooled, void* logits, int N, int HW, int C, int K,
+                     hipStream_t s);
+// dx [N, HW, C] = every pixel of image n gets bf16((dl . w) / HW)
+void launch_head_dx(const void* dl, const void* w, void* dx, int N, int HW,
+                    int C, int K, hipStream_t s);
+// dw fp32 [K, C], db fp32 [K] or null; acc_w / acc_b: add into the target
+// instead of overwriting it
+void launch_head_dw(const void* dl, const void* pooled, float* dw, float* db,
+                    int N, int C, int K, int acc_w, int acc_b, hipStream_t s);
+
 // ---- dgc.hip ---- (n is long long; compact's k is unsigned, scatter's
 // long long)
 int dgc_workspace_words();

@@ -1376,6 +1376,107 @@ torch::Tensor avgpool2x2_bwd(torch::Tensor dy, int64_t H, int64_t W) {
   return dx;
 }
 
+// ---- head.hip: global avg-pool + FC --------------------------------------
+
+// a dense GPU tensor of the given dtype at a 16-byte aligned address
+void check_head_operand(const torch::Tensor& t, torch::ScalarType dt,
+                        const torch::Tensor& like, const char* who) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt, who, ": GPU ",
+              c10::toString(dt), " tensor required");
+  TORCH_CHECK(t.device() == like.device(), who, ": operands on one device");
+  TORCH_CHECK(t.is_contiguous(), who, ": dense (contiguous) tensor required");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, who,
+              ": 16-byte aligned storage required");
+}
+
+void check_head_range(int64_t N, int64_t HW, int64_t C, int64_t K,
+                      const char* who) {
+  TORCH_CHECK(C % 64 == 0 && C >= 64 && C <= kHeadMaxC, who,
+              ": C % 64 == 0 and 64 <= C <= ", kHeadMaxC, " (got ", C, ")");
+  TORCH_CHECK(N >= 1 && N <= kHeadMaxRows, who, ": 1 <= N <= ", kHeadMaxRows,
+              " (got ", N, ")");
+  TORCH_CHECK(K >= 1 && HW >= 1, who, ": K >= 1 and H*W >= 1");
+  TORCH_CHECK(K <= (1 << 24), who, ": K <= 2^24");
+  TORCH_CHECK(N * HW * C < (1LL << 31), who, ": N*H*W*C < 2^31");
+}
+
+std::vector<torch::Tensor> head_fwd(torch::Tensor x, torch::Tensor w,
+                                    c10::optional<torch::Tensor> bias) {
+  check_nhwc_bf16(x, "head_fwd x");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "head_fwd x: 16-byte aligned storage required");
+  const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  check_head_operand(w, torch::kBFloat16, x, "head_fwd w");
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == C, "head_fwd w: [K, C] required");
+  const int64_t K = w.size(0);
+  check_head_range(N, HW, C, K, "head_fwd");
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    check_head_operand(*bias, torch::kFloat32, x, "head_fwd bias");
+    TORCH_CHECK(bias->dim() == 1 && bias->size(0) == K,
+                "head_fwd bias: fp32 [K] required");
+    bp = bias->data_ptr<float>();
+  }
+  auto opts = x.options().memory_format(torch::MemoryFormat::Contiguous);
+  auto pooled = torch::empty({N, C}, opts);
+  auto logits = torch::empty({N, K}, opts);
+  launch_head_fwd(x.data_ptr(), w.data_ptr(), bp, pooled.data_ptr(),
+                  logits.data_ptr(), (int)N, (int)HW, (int)C, (int)K,
+                  cur_stream());
+  return {logits, pooled};
+}
+
+py::tuple head_bwd(torch::Tensor dl, torch::Tensor pooled, torch::Tensor w,
+                   int64_t H, int64_t W, bool need_dx,
+                   c10::optional<torch::Tensor> dw_out,
+                   c10::optional<torch::Tensor> db_out) {
+  check_head_operand(dl, torch::kBFloat16, dl, "head_bwd dlogits");
+  check_head_operand(pooled, torch::kBFloat16, dl, "head_bwd pooled");
+  check_head_operand(w, torch::kBFloat16, dl, "head_bwd w");
+  TORCH_CHECK(dl.dim() == 2 && pooled.dim() == 2 && w.dim() == 2 &&
+                  dl.size(0) == pooled.size(0) && dl.size(1) == w.size(0) &&
+                  pooled.size(1) == w.size(1),
+              "head_bwd: dlogits [N, K], pooled [N, C], w [K, C] required");
+  TORCH_CHECK(H >= 1 && W >= 1, "head_bwd: H, W >= 1");
+  const int64_t N = dl.size(0), K = dl.size(1), C = w.size(1), HW = H * W;
+  check_head_range(N, HW, C, K, "head_bwd");
+  const bool acc_w = dw_out.has_value() && dw_out->defined();
+  const bool acc_b = db_out.has_value() && db_out->defined();
+  torch::Tensor dw, db;
+  auto f32 = dl.options().dtype(torch::kFloat32);
+  if (acc_w) {
+    check_head_operand(*dw_out, torch::kFloat32, dl, "head_bwd dw_out");
+    TORCH_CHECK(dw_out->dim() == 2 && dw_out->size(0) == K &&
+                    dw_out->size(1) == C,
+                "head_bwd dw_out: fp32 [K, C] required");
+    dw = *dw_out;
+  } else {
+    dw = torch::empty({K, C}, f32);
+  }
+  if (acc_b) {
+    check_head_operand(*db_out, torch::kFloat32, dl, "head_bwd db_out");
+    TORCH_CHECK(db_out->dim() == 1 && db_out->size(0) == K,
+                "head_bwd db_out: fp32 [K] required");
+    db = *db_out;
+  } else {
+    db = torch::empty({K}, f32);
+  }
+  py::object dx_o = py::none();
+  if (need_dx) {
+    auto dx = torch::empty(
+        {N, C, H, W},
+        dl.options().memory_format(torch::MemoryFormat::ChannelsLast));
+    launch_head_dx(dl.data_ptr(), w.data_ptr(), dx.data_ptr(), (int)N, (int)HW,
+                   (int)C, (int)K, cur_stream());
+    dx_o = py::cast(dx);
+  }
+  launch_head_dw(dl.data_ptr(), pooled.data_ptr(), dw.data_ptr<float>(),
+                 db.data_ptr<float>(), (int)N, (int)C, (int)K, acc_w ? 1 : 0,
+                 acc_b ? 1 : 0, cur_stream());
+  return py::make_tuple(dx_o, acc_w ? py::object(py::none()) : py::cast(dw),
+                        acc_b ? py::object(py::none()) : py::cast(db));
+}
+
 torch::Tensor conv3x3_wgrad_operand_padded(torch::Tensor xp, int64_t H,
                                            int64_t W, int64_t stride) {
   // xp: zero-halo padded conv input [N, H+2, W+2, Cin] -> [9*Cin, Mp]
@@ -1957,5 +2058,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("maxpool3x3s2_bwd", &maxpool3x3s2_bwd,
         "3x3/s2/p1 max pool backward (bounded gather via tap idx)");
   m.def("avgpool2x2_bwd", &avgpool2x2_bwd, "2x2/s2 ceil avg pool backward");
+  m.def("head_fwd", &head_fwd,
+        "global avg-pool + FC forward -> (logits bf16 [N,K], pooled bf16 [N,C])",
+        py::arg("x"), py::arg("w"), py::arg("bias") = py::none());
+  m.def("head_bwd", &head_bwd,
+        "global avg-pool + FC backward -> (dx | None, dW fp32 | None, db fp32 "
+        "| None); dw_out / db_out: fp32 targets to add into",
+        py::arg("dlogits"), py::arg("pooled"), py::arg("w"), py::arg("H"),
+        py::arg("W"), py::arg("need_dx"), py::arg("dw_out") = py::none(),
+        py::arg("db_out") = py::none());
   m.attr("_arch") = "gfx950";
 }

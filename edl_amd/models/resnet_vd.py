@@ -15,6 +15,7 @@ import torch.nn as nn
 
 from ..ops.bnrelu import BNAddReLU2d, BNReLU2d
 from ..ops.conv import Conv2dFast, conv_bn, eval_pair
+from ..ops.head import pool_linear
 from ..ops.pool import AvgPool2x2, MaxPool3x3s2
 
 
@@ -159,8 +160,8 @@ class ResNetVd(nn.Module):
 
     def forward(self, x):
         x = self.stages(self.stem(x))
-        x = self.avgpool(x).flatten(1)
-        return self.fc(x)
+        # fc(avgpool(x).flatten(1)); both stay attributes for the state dict
+        return pool_linear(x, self.fc)
 
 
 def resnet18_vd(num_classes=1000):

@@ -9,6 +9,7 @@ import torch.nn as nn
 
 from ..ops.bnrelu import BNAddReLU2d, BNReLU2d
 from ..ops.conv import Conv2dFast, conv_bn
+from ..ops.head import pool_linear
 from ..ops.pool import MaxPool3x3s2
 
 
@@ -76,7 +77,8 @@ class ResNeXtWSL(nn.Module):
     def forward(self, x):
         x = self.maxpool(self.bn1(self.conv1(x)))
         x = self.stages(x)
-        return self.fc(self.avgpool(x).flatten(1))
+        # fc(avgpool(x).flatten(1)); both stay attributes for the state dict
+        return pool_linear(x, self.fc)
 
 
 def resnext101_32x16d_wsl(num_classes=1000):
