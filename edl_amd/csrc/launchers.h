@@ -224,6 +224,23 @@ void launch_conv3x3s2_dgrad_grouped(const void* dyp, const void* wcat_g,
                                     void* dx, int Nimg, int H, int W, int C,
                                     int gw, int Hop, int Wop, hipStream_t s);
 
+// ---- conv7x7.hip ---- (7x7 stride-2 pad-3 stem conv, Cin <= 4 -> 64;
+// Nimg, H, W are the INPUT extents everywhere; Ho = (H-1)/2+1, Wo likewise)
+// x [N, H, W, Cin] -> xp [N, 2*Ho+5, 2*Wo+6, 4], halo and pad channels zero;
+// N*Hp*Wp*4 < 2^31 is the caller's to check
+void launch_pad_stem7(const void* x, void* xp, int Nimg, int H, int W,
+                      int Cin, hipStream_t s);
+int conv7x7s2_tiles(int Nimg, int H, int W);         // 16x16 output tiles
+int conv7x7s2_grid(int tiles, int max_blocks);       // persistent blocks
+// w7 [64, 224] bf16 (k = ky*32 + kx*4 + c), y [N*Ho*Wo, 64] bf16; max_blocks
+// caps the persistent grid (0 = the default cap)
+void launch_conv7x7s2(const void* xp, const void* w7, void* y, int Nimg,
+                      int H, int W, int max_blocks, hipStream_t s);
+// + the eval BN(+ReLU) apply in the epilogue; scale, shift fp32 [64]
+void launch_conv7x7s2_bn(const void* xp, const void* w7, void* y, int Nimg,
+                         int H, int W, const float* scale, const float* shift,
+                         bool relu, int max_blocks, hipStream_t s);
+
 // ---- gemm_tn.hip ---- (3x3: Cout, Cin, M, then Ho, Wo, Hp, Wp; the small
 // launcher puts CinP BEFORE stride, the others end stride, splitk, perm)
 void launch_gemm_tn_splitk(const void* A, const void* B, float* C, int N1,

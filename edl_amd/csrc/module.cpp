@@ -1756,6 +1756,64 @@ torch::Tensor conv3x3_fwd_bn_padded(torch::Tensor xp, torch::Tensor w3,
   return y;
 }
 
+// ---- 7x7 stride-2 pad-3 stem conv, Cin <= 4 -> 64 (conv7x7.hip) ---------
+// x [N, Cin, H, W] channels_last bf16; w7 [64, 224] the zero-padded repack
+// (conv.py _repack_w7: k = ky*32 + kx*4 + c). The input is
+// padded into a scratch buffer here on every call; nobody keeps it.
+// affine: scale/shift fp32 [64] for the eval BN(+ReLU) epilogue, or null.
+torch::Tensor conv7x7s2_impl(const torch::Tensor& x, const torch::Tensor& w7,
+                             const torch::Tensor* scale,
+                             const torch::Tensor* shift, bool relu,
+                             int64_t max_blocks, const char* who) {
+  check_nhwc_bf16(x, who);
+  const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(Cin >= 1 && Cin <= 4, who, ": Cin <= 4 required, got ", Cin);
+  TORCH_CHECK(H >= 1 && W >= 1, who, ": H, W >= 1 required");
+  TORCH_CHECK(w7.scalar_type() == torch::kBFloat16, who, ": w7 bf16 only");
+  TORCH_CHECK(w7.is_cuda() && w7.device() == x.device(), who,
+              ": w7 on another device than the input");
+  TORCH_CHECK(w7.dim() == 2 && w7.size(0) == 64 && w7.size(1) == 224, who,
+              ": w7 shape [64, 224] required");
+  TORCH_CHECK(w7.is_contiguous(), who, ": w7 not contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(w7.data_ptr()) % 16 == 0, who,
+              ": w7 base not 16-byte aligned");
+  if (scale != nullptr) check_bn_affine(*scale, *shift, 64, x, who);
+  TORCH_CHECK(max_blocks >= 0, who, ": max_blocks >= 0");
+  const int64_t Ho = out_extent(H, 2), Wo = out_extent(W, 2);
+  const int64_t Hp = 2 * Ho + 5, Wp = 2 * Wo + 6;
+  TORCH_CHECK(N * Hp * Wp * 4 < (1LL << 31), who,
+              ": padded input must stay below 2^31 elements");
+  auto y = torch::empty({N * Ho * Wo, 64}, x.options());
+  if (N == 0) return y;
+  auto s = cur_stream();
+  auto xp = torch::empty({N, Hp, Wp, 4}, x.options());
+  launch_pad_stem7(x.data_ptr(), xp.data_ptr(), (int)N, (int)H, (int)W,
+                   (int)Cin, s);
+  const int mb = (int)std::min<int64_t>(max_blocks, 1 << 20);
+  if (scale != nullptr)
+    launch_conv7x7s2_bn(xp.data_ptr(), w7.data_ptr(), y.data_ptr(), (int)N,
+                        (int)H, (int)W, scale->data_ptr<float>(),
+                        shift->data_ptr<float>(), relu, mb, s);
+  else
+    launch_conv7x7s2(xp.data_ptr(), w7.data_ptr(), y.data_ptr(), (int)N,
+                     (int)H, (int)W, mb, s);
+  return y;
+}
+
+torch::Tensor conv7x7s2_fwd(torch::Tensor x, torch::Tensor w7,
+                            int64_t max_blocks) {
+  return conv7x7s2_impl(x, w7, nullptr, nullptr, false, max_blocks,
+                        "conv7x7s2");
+}
+
+// conv7x7s2_fwd followed by bn_fwd_eval (no residual), bit for bit
+torch::Tensor conv7x7s2_fwd_bn(torch::Tensor x, torch::Tensor w7,
+                               torch::Tensor scale, torch::Tensor shift,
+                               bool relu, int64_t max_blocks) {
+  return conv7x7s2_impl(x, w7, &scale, &shift, relu, max_blocks,
+                        "conv7x7s2_bn");
+}
+
 // the unpadded twins: x 4-D channels_last bf16 [N, C, H, W], padded here
 torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
   check_nhwc_bf16(x, "conv3x3", 64);
@@ -2024,6 +2082,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3_grouped_fwd_bn", &conv3x3_grouped_fwd_bn,
         "conv3x3_grouped_fwd + eval BN(+ReLU) apply in the epilogue: (x, "
         "w3g, stride, scale, shift, relu) -> y2d");
+  m.def("conv7x7s2_fwd", &conv7x7s2_fwd, py::arg("x"), py::arg("w7"),
+        py::arg("max_blocks") = 0,
+        "7x7 stride-2 pad-3 stem conv, Cin <= 4 -> 64: y2d [N*Ho*Wo, 64]; "
+        "max_blocks caps the persistent grid (0 = default)");
+  m.def("conv7x7s2_fwd_bn", &conv7x7s2_fwd_bn, py::arg("x"), py::arg("w7"),
+        py::arg("scale"), py::arg("shift"), py::arg("relu"),
+        py::arg("max_blocks") = 0,
+        "conv7x7s2_fwd + eval BN(+ReLU) apply in the epilogue, bit-equal to "
+        "bn_fwd_eval(conv7x7s2_fwd(x, w7), scale, shift, None, relu)");
   m.def("transpose_pad", &transpose_pad,
         "bf16 [M,C] -> [C, ceil64(M)] transpose with zero pad");
   m.def("gemm_bt_splitk", &gemm_bt_splitk,

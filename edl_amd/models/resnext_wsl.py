@@ -75,7 +75,8 @@ class ResNeXtWSL(nn.Module):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
 
     def forward(self, x):
-        x = self.maxpool(self.bn1(self.conv1(x)))
+        # bn1(conv1(x)); in inference the 7x7 stem kernel applies bn1 itself
+        x = self.maxpool(conv_bn(self.conv1, self.bn1, x))
         x = self.stages(x)
         # fc(avgpool(x).flatten(1)); both stay attributes for the state dict
         return pool_linear(x, self.fc)

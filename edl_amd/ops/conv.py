@@ -6,7 +6,9 @@ ROCm), which runs far closer to the MFMA roofline than MIOpen's igemm
 path at these shapes (igemm measured ~2-4% of bf16 peak at bs32, by
 rocprof). 3x3 same-pad convolutions run the in-repo implicit-GEMM kernels
 (dense C % 64, small-channel stem, grouped ResNeXt shapes — forward and
-backward); everything else stays on F.conv2d (MIOpen).
+backward), and the 7x7 stride-2 stem of the ResNeXt teacher (Cin <= 4 -> 64)
+runs its forward on the in-repo conv7x7 kernel (weight gradient from the
+library); everything else stays on F.conv2d (MIOpen).
 
 Weight layout stays nn.Conv2d-compatible ([Cout, Cin, kh, kw]) so state
 dicts interchange."""
@@ -419,6 +421,51 @@ class _Conv3x3SmallHip(torch.autograd.Function):
         return dx, dw, None, None, None, None, None
 
 
+# The 7x7 stride-2 pad-3 stem (ResNeXt teacher conv1) runs its forward on
+# conv7x7.hip, alone or with the eval BN+ReLU in its epilogue (conv_bn).
+# 0 = nn.Conv2d (MIOpen, with its per-input-shape find phase), as before.
+_CONV7X7 = os.environ.get("EDL_CONV7X7", "1") == "1"
+
+
+def _repack_w7(weight):
+    """[64, Cin<=4, 7, 7] -> [64, 7, 8, 4] -> [64, 224] bf16 for the 7x7
+    stem kernel: entry [co, ky, kx, c] = w[co, c, ky, kx]; the kx = 7 slot
+    and the channels >= Cin are zero (one MFMA k-step is one filter row of
+    8 kx slots x 4 channels)."""
+    co, ci = weight.shape[0], weight.shape[1]
+    out = torch.zeros(co, 7, 8, 4, dtype=torch.bfloat16, device=weight.device)
+    out[:, :, :7, :ci] = weight.detach().permute(0, 2, 3, 1).to(torch.bfloat16)
+    return out.reshape(co, 224)
+
+
+class _Conv7x7Hip(torch.autograd.Function):
+    """7x7 stride-2 pad-3 stem conv (Conv2dFast._is_stem7x7 shapes): the
+    forward on the in-repo implicit-GEMM kernel. The weight gradient is
+    torch.nn.grad.conv2d_weight on the saved input, the route
+    _Conv3x3SmallHip takes by default and for the same reason; there is no
+    input gradient (the input is the image: forward() keeps an input that
+    requires one on nn.Conv2d)."""
+
+    @staticmethod
+    def forward(ctx, x, w_param, w7):
+        ctx.save_for_backward(x)
+        ctx.w_dtype = w_param.dtype
+        ctx.w_shape = tuple(w_param.shape)
+        n, _, h, w = x.shape
+        return _nchw_view(ext().conv7x7s2_fwd(x, w7), n, *_out_hw(h, w, 2))
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        dyb = dy.contiguous(memory_format=torch.channels_last).to(
+            torch.bfloat16)
+        dw = torch.nn.grad.conv2d_weight(x, ctx.w_shape, dyb, stride=(2, 2),
+                                         padding=(3, 3))
+        if dw.dtype != ctx.w_dtype:
+            dw = dw.to(ctx.w_dtype)
+        return None, dw, None
+
+
 _S2D_TAP_ORDER = [(1, 1), (1, 0), (1, 2), (0, 1), (2, 1),
                   (0, 0), (0, 2), (2, 0), (2, 2)]
 
@@ -678,6 +725,18 @@ class Conv2dFast(nn.Conv2d):
                 and cpg in (16, 32, 64, 128)
                 and self.in_channels % 64 == 0)
 
+    def _is_stem7x7(self):
+        """The ResNeXt teacher's conv1: 7x7, stride 2, padding 3, up to 4
+        input channels, 64 output channels, no bias (conv7x7.hip)."""
+        return (self.kernel_size == (7, 7)
+                and self.stride == (2, 2)
+                and self.padding == (3, 3)
+                and self.dilation == (1, 1)
+                and self.groups == 1
+                and self.bias is None
+                and self.out_channels == 64
+                and self.in_channels <= 4)
+
     def takes_padded(self):
         """True if this conv runs the padded-input 3x3 kernels and wants
         the producing BN to write the padded layout (x._edl_xp)."""
@@ -731,6 +790,11 @@ class Conv2dFast(nn.Conv2d):
                     return self._forward_grouped3x3(x)
                 if _GROUPED_TRAIN:
                     return self._forward_grouped3x3_train(x)
+            if (_CONV7X7 and self._is_stem7x7()
+                    and (bf16 or (x.dtype == torch.float32
+                                  and torch.is_autocast_enabled()))
+                    and not (x.requires_grad and torch.is_grad_enabled())):
+                return self._forward_stem7x7(x)
         if (
             _CONV1X1 != "miopen"
             and x.is_cuda
@@ -821,6 +885,18 @@ class Conv2dFast(nn.Conv2d):
             self._bn_part = holder[0]
         return y
 
+    def _stem7x7_operands(self, x):
+        """(x as bf16 channels_last, w7) for the 7x7 stem kernel."""
+        if x.dtype != torch.bfloat16:
+            x = x.to(torch.bfloat16)  # the cast autocast would do
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            x = x.contiguous(memory_format=torch.channels_last)
+        return x, self._cached("w7", lambda: _repack_w7(self.weight))
+
+    def _forward_stem7x7(self, x):
+        x, w7 = self._stem7x7_operands(x)
+        return _Conv7x7Hip.apply(x, self.weight, w7)
+
     def _forward_grouped3x3(self, x):
         if not x.is_contiguous(memory_format=torch.channels_last):
             x = x.contiguous(memory_format=torch.channels_last)
@@ -898,10 +974,17 @@ class Conv2dFast(nn.Conv2d):
     def _eval_bn_route(self, x):
         """Which in-repo kernel forward(x) would run on this bf16 GPU input
         with autograd off, among those that carry the BN epilogue: "1x1",
-        "dense3x3", "grouped3x3", or None (the stem kernels, MIOpen, the
-        matmul route). Mirrors the order of the checks in forward."""
-        if not (x.is_cuda and available() and x.dtype == torch.bfloat16
-                and x.dim() == 4):
+        "dense3x3", "grouped3x3", "stem7x7", or None (the 3x3 stem kernel,
+        MIOpen, the matmul route). Mirrors the order of the checks in
+        forward. The 7x7 stem casts its own input, so it alone also takes
+        an fp32 input under autocast."""
+        if not (x.is_cuda and available() and x.dim() == 4):
+            return None
+        if x.dtype != torch.bfloat16:
+            if (x.dtype == torch.float32 and torch.is_autocast_enabled()
+                    and _CONV3X3 == "hip" and _CONV7X7
+                    and self._is_stem7x7()):
+                return "stem7x7"
             return None
         if _CONV3X3 == "hip":
             if self._is_dense3x3():
@@ -911,6 +994,8 @@ class Conv2dFast(nn.Conv2d):
                 return None
             if self._is_grouped3x3():
                 return "grouped3x3"
+            if _CONV7X7 and self._is_stem7x7():
+                return "stem7x7"
         if (_CONV1X1 == "hip" and self.kernel_size == (1, 1)
                 and self.groups == 1 and self.padding == (0, 0)
                 and self.bias is None and self.in_channels % 64 == 0
@@ -944,8 +1029,12 @@ class Conv2dFast(nn.Conv2d):
                 res2d = res.permute(0, 2, 3, 1).reshape(n * h * w, co)
             y2d = e.gemm_bt_bn(x2d, w_bf16, scale, shift, relu, res2d)
             return _nchw_view(y2d, n, h, w)
-        assert res is None  # the 3x3 epilogues carry no residual
+        assert res is None  # the 3x3 / 7x7 epilogues carry no residual
         n, _, h, w = x.shape
+        if route == "stem7x7":
+            x, w7 = self._stem7x7_operands(x)
+            y2d = e.conv7x7s2_fwd_bn(x, w7, scale, shift, relu)
+            return _nchw_view(y2d, n, *_out_hw(h, w, 2))
         if route == "grouped3x3":
             if not x.is_contiguous(memory_format=torch.channels_last):
                 x = x.contiguous(memory_format=torch.channels_last)
@@ -983,12 +1072,12 @@ def conv_bn(conv, bn, x, res=None):
 
     Exactly where that expression would run BOTH in-repo kernels in
     inference — the conv on its hip route (1x1 at any stride, dense 3x3,
-    grouped 3x3) and the BN's fused eval apply — one kernel runs instead:
-    the conv with the BN's scale/shift (+ residual) (+ ReLU) in its epilogue.
-    The 3x3 kernels carry no residual. Everywhere else (training, autograd
-    on, CPU, fp32, the stem kernels, MIOpen routes, a BN on its torch
-    fallback, a residual the epilogue cannot read in place) the two modules
-    are called as written above."""
+    grouped 3x3, the 7x7 stem) and the BN's fused eval apply — one kernel
+    runs instead: the conv with the BN's scale/shift (+ residual) (+ ReLU)
+    in its epilogue. The 3x3 and 7x7 kernels carry no residual. Everywhere
+    else (training, autograd on, CPU, fp32, the 3x3 stem kernel, MIOpen
+    routes, a BN on its torch fallback, a residual the epilogue cannot read
+    in place) the two modules are called as written above."""
     if eval_pair(bn) and bn.num_features == conv.out_channels:
         route = conv._eval_bn_route(x)
         if route is not None and res is not None:

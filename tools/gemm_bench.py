@@ -4,6 +4,7 @@ conv1x1 shapes at bs32. Run on a GPU box:
     python tools/gemm_bench.py --dgrad-add   # fused residual-add dgrad
     python tools/gemm_bench.py --eval-bn     # conv1x1 + eval BN in one kernel
     python tools/gemm_bench.py --grouped-bwd # grouped 3x3 dgrad/wgrad vs MIOpen
+    python tools/gemm_bench.py --stem7       # 7x7/s2 stem conv vs MIOpen
 """
 import os
 import sys
@@ -313,8 +314,59 @@ def main_grouped_bwd(batch=16, windows=9, l3_bytes=256 << 20):
             torch.cuda.empty_cache()
 
 
+# (N, H, W) of the 7x7 stride-2 stem conv, 3 -> 64 channels: the teacher's
+# serving batches and one small shape (launch-bound; it fits every cache)
+STEM7_SHAPES = [(16, 224, 224), (32, 224, 224), (4, 112, 112)]
+
+
+def main_stem7(windows=9, l3_bytes=256 << 20, max_sets=64):
+    """7x7/s2 stem conv -> eval BN+ReLU per input shape: (a) the library
+    conv (F.conv2d on channels_last bf16) + bn_fwd_eval, (b) conv7x7s2_fwd +
+    bn_fwd_eval, (c) conv7x7s2_fwd_bn, (d) conv7x7s2_fwd alone. Cold operands
+    and timing as --dgrad-add (at most max_sets sets). GB/s of (d): input
+    read + output written once, over its median."""
+    import torch.nn.functional as F
+    from edl_amd.ops.conv import _repack_w7
+    e = ops.ext()
+    cl = torch.channels_last
+    w = (torch.randn(64, 3, 7, 7, device="cuda") * 0.05).to(
+        torch.bfloat16).contiguous(memory_format=cl)
+    w7 = _repack_w7(w)
+    sc, sh = torch.randn(64, device="cuda"), torch.randn(64, device="cuda")
+    print("%-16s %-26s %-26s %-26s %-26s %8s" % (
+        "(N,H,W)", "(a) library + bn_apply", "(b) conv7x7 + bn_apply",
+        "(c) conv7x7_bn", "(d) conv7x7 alone", "(d) GB/s"))
+    for n, h, wd in STEM7_SHAPES:
+        ho, wo = (h - 1) // 2 + 1, (wd - 1) // 2 + 1
+        set_bytes = 2 * n * (3 * h * wd + 64 * ho * wo)
+        nsets = min(max_sets, max(2, -(-int(1.25 * l3_bytes) // set_bytes)))
+        sets = [(torch.randn(n, 3, h, wd, device="cuda").to(
+            torch.bfloat16).contiguous(memory_format=cl),)
+            for _ in range(nsets)]
+        fns = {
+            "a": lambda x: e.bn_fwd_eval(
+                F.conv2d(x, w, stride=2, padding=3).permute(0, 2, 3, 1)
+                .reshape(-1, 64), sc, sh, None, True),
+            "b": lambda x: e.bn_fwd_eval(e.conv7x7s2_fwd(x, w7), sc, sh,
+                                         None, True),
+            "c": lambda x: e.conv7x7s2_fwd_bn(x, w7, sc, sh, True),
+            "d": lambda x: e.conv7x7s2_fwd(x, w7),
+        }
+        cols, med = [], {}
+        for key in ("a", "b", "c", "d"):
+            us = _graph_us(fns[key], sets, windows)
+            med[key] = us[len(us) // 2]
+            cols.append("%8.1f [%7.1f..%7.1f]" % (med[key], us[0], us[-1]))
+        print("%-16s %-26s %-26s %-26s %-26s %8.0f" % (
+            str((n, h, wd)), *cols, set_bytes / med["d"] / 1e3), flush=True)
+        del sets
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
-    if "--grouped-bwd" in sys.argv:
+    if "--stem7" in sys.argv:
+        main_stem7()
+    elif "--grouped-bwd" in sys.argv:
         main_grouped_bwd()
     elif "--dgrad-add" in sys.argv:
         main_dgrad_add()

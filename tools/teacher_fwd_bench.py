@@ -14,6 +14,13 @@ kernel, ops.conv.conv_bn): 0 and 1 interleaved in one process over --rounds
 rounds, with the outputs of the two settings compared.
 
     python tools/teacher_fwd_bench.py --eval-fuse --iters 30 --warmup 8
+
+--stem7 A/Bs EDL_CONV7X7 (the 7x7 stem on the in-repo kernel) the same way;
+with --cold-batch B it reports, for the one setting the environment selects,
+the first forward at a batch size the process has not seen before.
+
+    python tools/teacher_fwd_bench.py --stem7 --iters 30 --warmup 8
+    EDL_CONV7X7=0 python tools/teacher_fwd_bench.py --stem7 --cold-batch 24
 """
 import argparse
 import json
@@ -78,6 +85,60 @@ def eval_fuse_ab(args, m, x):
                       "rel_err_randn": round(err, 5)}))
 
 
+def stem7_ab(args, m, x):
+    """EDL_CONV7X7 0 (the library stem conv + its own BN launch) vs 1 (the
+    in-repo 7x7 kernel with the BN in its epilogue), interleaved over
+    --rounds rounds. With --cold-batch B instead: ONE setting per process
+    (EDL_CONV7X7 from the environment); after the warm-up at --batch, the
+    wall time of the first forward at batch B, a shape the process has not
+    seen, is reported."""
+    import torch
+
+    import edl_amd.ops.conv as conv_mod
+
+    if args.cold_batch:
+        _timed(m, x, args.warmup, 1)
+        xc = torch.randn(args.cold_batch, 3, 224, 224, device="cuda")
+        xc = xc.contiguous(memory_format=torch.channels_last)
+        torch.cuda.synchronize()
+        t0 = time.monotonic()
+        with torch.no_grad(), torch.autocast("cuda", torch.bfloat16):
+            m(xc)
+        torch.cuda.synchronize()
+        first = time.monotonic() - t0
+        dt, _ = _timed(m, xc, 2, args.iters)
+        print(json.dumps({"bench": "teacher_fwd_cold_shape",
+                          "EDL_CONV7X7": int(conv_mod._CONV7X7),
+                          "warm_batch": args.batch,
+                          "cold_batch": args.cold_batch,
+                          "first_fwd_ms": round(first * 1000, 2),
+                          "steady_ms": round(dt * 1000, 3)}))
+        return
+
+    assert args.rounds >= 3, "--rounds: at least three"
+    out = {}
+    for on in (False, True):
+        conv_mod._CONV7X7 = on
+        with torch.no_grad(), torch.autocast("cuda", torch.bfloat16):
+            out[on] = m(x).float()
+    d = (out[True] - out[False]).abs()
+    err = float((d / out[False].abs().mean().clamp(min=0.05)).max().item())
+    print("randn input: rel err vs the library stem = %.4g" % err, flush=True)
+    ms = {False: [], True: []}
+    for r in range(args.rounds):
+        for on in (False, True):
+            conv_mod._CONV7X7 = on
+            dt, _ = _timed(m, x, args.warmup, args.iters)
+            ms[on].append(round(dt * 1000, 3))
+            print("[round %d EDL_CONV7X7=%d] %7.3f ms/fwd  %8.1f img/s" %
+                  (r, on, dt * 1000, args.batch / dt), flush=True)
+    print(json.dumps({"bench": "teacher_fwd_stem7", "model": args.model,
+                      "batch": args.batch, "iters": args.iters,
+                      "ms_per_fwd_library": ms[False],
+                      "ms_per_fwd_conv7x7": ms[True],
+                      "rel_err_randn": round(err, 5)}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=16)
@@ -85,6 +146,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--model", default="resnext101_32x16d_wsl")
     ap.add_argument("--eval-fuse", action="store_true")
+    ap.add_argument("--stem7", action="store_true")
+    ap.add_argument("--cold-batch", type=int, default=0)
     ap.add_argument("--rounds", type=int, default=3)
     args = ap.parse_args()
 
@@ -103,6 +166,8 @@ def main():
 
     if args.eval_fuse:
         return eval_fuse_ab(args, m, x)
+    if args.stem7:
+        return stem7_ab(args, m, x)
 
     results = {}
     ref = None
