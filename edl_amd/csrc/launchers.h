@@ -241,6 +241,17 @@ void launch_conv7x7s2_bn(const void* xp, const void* w7, void* y, int Nimg,
                          int H, int W, const float* scale, const float* shift,
                          bool relu, int max_blocks, hipStream_t s);
 
+// ---- conv7x7_wgrad.hip ---- (weight gradient of the stem conv above on the
+// same xp; Nimg, H, W again the INPUT extents)
+// persistent blocks = rows of `part` (max_blocks 0 = the default cap)
+int conv7x7s2_wgrad_grid(int tiles, int max_blocks);
+// dy [N*Ho*Wo, 64] bf16, part fp32 [conv7x7s2_wgrad_grid(conv7x7s2_tiles(..),
+// max_blocks), 64*224] (every row written), dw fp32 [64, Cin, 7, 7]; two
+// launches: the partial kernel, then the fixed-order fold
+void launch_conv7x7s2_wgrad(const void* xp, const void* dy, float* part,
+                            float* dw, int Nimg, int H, int W, int Cin,
+                            int max_blocks, hipStream_t s);
+
 // ---- gemm_tn.hip ---- (3x3: Cout, Cin, M, then Ho, Wo, Hp, Wp; the small
 // launcher puts CinP BEFORE stride, the others end stride, splitk, perm)
 void launch_gemm_tn_splitk(const void* A, const void* B, float* C, int N1,

@@ -1814,6 +1814,49 @@ torch::Tensor conv7x7s2_fwd_bn(torch::Tensor x, torch::Tensor w7,
                         "conv7x7s2_bn");
 }
 
+// Weight gradient of the same conv (conv7x7_wgrad.hip): x as the forward
+// takes it, dy2d [N*Ho*Wo, 64] bf16 -> dW fp32 [64, Cin, 7, 7]. x is padded
+// again here (the forward keeps its xp to itself); the partial rows live for
+// this call only.
+torch::Tensor conv7x7s2_wgrad(torch::Tensor x, torch::Tensor dy2d,
+                              int64_t max_blocks) {
+  const char* who = "conv7x7s2_wgrad";
+  check_nhwc_bf16(x, who);
+  const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(Cin >= 1 && Cin <= 4, who, ": Cin <= 4 required, got ", Cin);
+  TORCH_CHECK(H >= 1 && W >= 1, who, ": H, W >= 1 required");
+  const int64_t Ho = out_extent(H, 2), Wo = out_extent(W, 2);
+  const int64_t Hp = 2 * Ho + 5, Wp = 2 * Wo + 6;
+  TORCH_CHECK(N * Hp * Wp * 4 < (1LL << 31), who,
+              ": padded input must stay below 2^31 elements");
+  TORCH_CHECK(dy2d.scalar_type() == torch::kBFloat16, who, ": dy2d bf16 only");
+  TORCH_CHECK(dy2d.is_cuda() && dy2d.device() == x.device(), who,
+              ": dy2d on another device than the input");
+  TORCH_CHECK(dy2d.dim() == 2 && dy2d.size(1) == 64, who,
+              ": dy2d [N*Ho*Wo, 64] required");
+  TORCH_CHECK(dy2d.size(0) == N * Ho * Wo, who, ": dy2d has ", dy2d.size(0),
+              " rows, the input gives ", N * Ho * Wo);
+  TORCH_CHECK(dy2d.is_contiguous(), who, ": dy2d not contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dy2d.data_ptr()) % 16 == 0, who,
+              ": dy2d base not 16-byte aligned");
+  TORCH_CHECK(max_blocks >= 0, who, ": max_blocks >= 0");
+  const auto f32 = x.options().dtype(torch::kFloat32);
+  auto dw = torch::empty({64, Cin, 7, 7}, f32);
+  const int mb = (int)std::min<int64_t>(max_blocks, 1 << 20);
+  const int rows =
+      conv7x7s2_wgrad_grid(conv7x7s2_tiles((int)N, (int)H, (int)W), mb);
+  auto s = cur_stream();
+  auto xp = torch::empty({N, Hp, Wp, 4}, x.options());
+  auto part = torch::empty({rows, 64 * 224}, f32);
+  if (N > 0)
+    launch_pad_stem7(x.data_ptr(), xp.data_ptr(), (int)N, (int)H, (int)W,
+                     (int)Cin, s);
+  launch_conv7x7s2_wgrad(xp.data_ptr(), dy2d.data_ptr(),
+                         part.data_ptr<float>(), dw.data_ptr<float>(), (int)N,
+                         (int)H, (int)W, (int)Cin, mb, s);
+  return dw;
+}
+
 // the unpadded twins: x 4-D channels_last bf16 [N, C, H, W], padded here
 torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
   check_nhwc_bf16(x, "conv3x3", 64);
@@ -2091,6 +2134,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("max_blocks") = 0,
         "conv7x7s2_fwd + eval BN(+ReLU) apply in the epilogue, bit-equal to "
         "bn_fwd_eval(conv7x7s2_fwd(x, w7), scale, shift, None, relu)");
+  m.def("conv7x7s2_wgrad", &conv7x7s2_wgrad, py::arg("x"), py::arg("dy2d"),
+        py::arg("max_blocks") = 0,
+        "weight gradient of the 7x7 stride-2 stem conv: x as conv7x7s2_fwd "
+        "takes it, dy2d [N*Ho*Wo, 64] bf16 -> fp32 [64, Cin, 7, 7]; "
+        "max_blocks caps the persistent grid (0 = default)");
   m.def("transpose_pad", &transpose_pad,
         "bf16 [M,C] -> [C, ceil64(M)] transpose with zero pad");
   m.def("gemm_bt_splitk", &gemm_bt_splitk,

@@ -7,8 +7,8 @@ path at these shapes (igemm measured ~2-4% of bf16 peak at bs32, by
 rocprof). 3x3 same-pad convolutions run the in-repo implicit-GEMM kernels
 (dense C % 64, small-channel stem, grouped ResNeXt shapes — forward and
 backward), and the 7x7 stride-2 stem of the ResNeXt teacher (Cin <= 4 -> 64)
-runs its forward on the in-repo conv7x7 kernel (weight gradient from the
-library); everything else stays on F.conv2d (MIOpen).
+runs its forward and its weight gradient on the in-repo conv7x7 kernels;
+everything else stays on F.conv2d (MIOpen).
 
 Weight layout stays nn.Conv2d-compatible ([Cout, Cin, kh, kw]) so state
 dicts interchange."""
@@ -425,6 +425,9 @@ class _Conv3x3SmallHip(torch.autograd.Function):
 # conv7x7.hip, alone or with the eval BN+ReLU in its epilogue (conv_bn).
 # 0 = nn.Conv2d (MIOpen, with its per-input-shape find phase), as before.
 _CONV7X7 = os.environ.get("EDL_CONV7X7", "1") == "1"
+# Its weight gradient on conv7x7_wgrad.hip (ext().conv7x7s2_wgrad). 0 =
+# torch.nn.grad.conv2d_weight (MIOpen, find phase included), as before.
+_CONV7X7_WGRAD = os.environ.get("EDL_CONV7X7_WGRAD", "1") == "1"
 
 
 def _repack_w7(weight):
@@ -440,9 +443,9 @@ def _repack_w7(weight):
 
 class _Conv7x7Hip(torch.autograd.Function):
     """7x7 stride-2 pad-3 stem conv (Conv2dFast._is_stem7x7 shapes): the
-    forward on the in-repo implicit-GEMM kernel. The weight gradient is
-    torch.nn.grad.conv2d_weight on the saved input, the route
-    _Conv3x3SmallHip takes by default and for the same reason; there is no
+    forward on the in-repo implicit-GEMM kernel, the weight gradient on
+    conv7x7_wgrad.hip from the saved input (EDL_CONV7X7_WGRAD=0, or a dy off
+    the GPU: torch.nn.grad.conv2d_weight, as before); there is no
     input gradient (the input is the image: forward() keeps an input that
     requires one on nn.Conv2d)."""
 
@@ -459,8 +462,12 @@ class _Conv7x7Hip(torch.autograd.Function):
         (x,) = ctx.saved_tensors
         dyb = dy.contiguous(memory_format=torch.channels_last).to(
             torch.bfloat16)
-        dw = torch.nn.grad.conv2d_weight(x, ctx.w_shape, dyb, stride=(2, 2),
-                                         padding=(3, 3))
+        if _CONV7X7_WGRAD and dyb.is_cuda:
+            dw = ext().conv7x7s2_wgrad(
+                x, dyb.permute(0, 2, 3, 1).reshape(-1, 64))
+        else:
+            dw = torch.nn.grad.conv2d_weight(x, ctx.w_shape, dyb,
+                                             stride=(2, 2), padding=(3, 3))
         if dw.dtype != ctx.w_dtype:
             dw = dw.to(ctx.w_dtype)
         return None, dw, None

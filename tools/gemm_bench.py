@@ -5,6 +5,7 @@ conv1x1 shapes at bs32. Run on a GPU box:
     python tools/gemm_bench.py --eval-bn     # conv1x1 + eval BN in one kernel
     python tools/gemm_bench.py --grouped-bwd # grouped 3x3 dgrad/wgrad vs MIOpen
     python tools/gemm_bench.py --stem7       # 7x7/s2 stem conv vs MIOpen
+    python tools/gemm_bench.py --stem7-wgrad # its weight gradient vs MIOpen
 """
 import os
 import sys
@@ -363,8 +364,86 @@ def main_stem7(windows=9, l3_bytes=256 << 20, max_sets=64):
         torch.cuda.empty_cache()
 
 
+def _graph_us_alternating(fns, sets, windows):
+    """_graph_us for several variants at once: one captured pass over the
+    sets per variant, then `windows` rounds that replay every variant in
+    turn, so drift of the machine hits all columns alike. {key: sorted us}."""
+    graphs = {}
+    for key, fn in fns.items():
+        for ops_ in sets:  # warm-up pass (the library's find phase too)
+            fn(*ops_)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for ops_ in sets:
+                fn(*ops_)
+        g.replay()
+        graphs[key] = g
+    torch.cuda.synchronize()
+    us = {key: [] for key in fns}
+    for _ in range(windows):
+        for key, g in graphs.items():
+            t0 = torch.cuda.Event(enable_timing=True)
+            t1 = torch.cuda.Event(enable_timing=True)
+            t0.record()
+            g.replay()
+            t1.record()
+            torch.cuda.synchronize()
+            us[key].append(t0.elapsed_time(t1) * 1e3 / len(sets))
+    return {key: sorted(v) for key, v in us.items()}
+
+
+# max_blocks of conv7x7s2_wgrad timed next to its default (0)
+STEM7_WGRAD_BLOCKS = (64, 128, 192)
+
+
+def main_stem7_wgrad(windows=9, l3_bytes=256 << 20, max_sets=64):
+    """7x7/s2 stem weight gradient per input shape: (a)
+    torch.nn.grad.conv2d_weight on channels_last bf16 after its find phase,
+    (b) conv7x7s2_wgrad (pad launch and fold included) at the default grid
+    cap, then (b) at each max_blocks of STEM7_WGRAD_BLOCKS. All columns in
+    one process, replayed alternately; cold operands as --stem7. GB/s of
+    (b): dY + the padded input read once, over its median."""
+    e = ops.ext()
+    cl = torch.channels_last
+    keys = ["a", "b"] + ["b@%d" % mb for mb in STEM7_WGRAD_BLOCKS]
+    print(("%-16s" + " %-26s" * len(keys) + " %8s") % (
+        "(N,H,W)", "(a) library", "(b) conv7x7s2_wgrad",
+        *["(b) max_blocks %d" % mb for mb in STEM7_WGRAD_BLOCKS], "(b) GB/s"))
+    for n, h, wd in STEM7_SHAPES:
+        ho, wo = (h - 1) // 2 + 1, (wd - 1) // 2 + 1
+        set_bytes = 2 * n * (3 * h * wd + 64 * ho * wo)
+        read_bytes = 2 * n * (64 * ho * wo + 4 * (2 * ho + 5) * (2 * wo + 6))
+        nsets = min(max_sets, max(2, -(-int(1.25 * l3_bytes) // set_bytes)))
+        sets = [(torch.randn(n, 3, h, wd, device="cuda").to(
+            torch.bfloat16).contiguous(memory_format=cl),
+            torch.randn(n, 64, ho, wo, device="cuda").to(
+            torch.bfloat16).contiguous(memory_format=cl))
+            for _ in range(nsets)]
+
+        def hip(mb):
+            return lambda x, dy: e.conv7x7s2_wgrad(
+                x, dy.permute(0, 2, 3, 1).reshape(-1, 64), mb)
+
+        fns = {"a": lambda x, dy: torch.nn.grad.conv2d_weight(
+            x, (64, 3, 7, 7), dy, stride=(2, 2), padding=(3, 3)),
+            "b": hip(0)}
+        for mb in STEM7_WGRAD_BLOCKS:
+            fns["b@%d" % mb] = hip(mb)
+        us = _graph_us_alternating(fns, sets, windows)
+        cols = ["%8.1f [%7.1f..%7.1f]" % (u[len(u) // 2], u[0], u[-1])
+                for u in (us[k] for k in keys)]
+        med_b = us["b"][len(us["b"]) // 2]
+        print(("%-16s" + " %-26s" * len(keys) + " %8.0f") % (
+            str((n, h, wd)), *cols, read_bytes / med_b / 1e3), flush=True)
+        del sets
+        torch.cuda.empty_cache()
+
+
 if __name__ == "__main__":
-    if "--stem7" in sys.argv:
+    if "--stem7-wgrad" in sys.argv:
+        main_stem7_wgrad()
+    elif "--stem7" in sys.argv:
         main_stem7()
     elif "--grouped-bwd" in sys.argv:
         main_grouped_bwd()
