@@ -94,14 +94,16 @@ __device__ __forceinline__ bf16x8 lds_read16(const char* p) {
 
 }  // namespace
 
-// x [N, H, W, Cin] -> xp [N, Hp, Sp slots of 2 pixels x 4 channels]. One
+// x [N, H, W, Cin] -> xp [N, Hp, Sp slots of 2 pixels x 4 channels] with a
+// zero border of `halo` pixels above and to the left (3 here, 1 for the 3x3
+// stem wgrad, conv3x3_small_wgrad.hip). One
 // thread builds one slot in registers and stores it whole (16 B; see the
 // note in pad_nhwc_cpad_kernel on per-channel store loops). Halo, channels
 // >= Cin and the extra row / column of an odd H / W are zeros written here
 // on every launch: there is no fill launch to replay.
 extern "C" __global__ void pad_stem7_kernel(
     const bf16* __restrict__ x, bf16* __restrict__ xp, const int H,
-    const int W, const int Hp, const int Sp, const int Cin,
+    const int W, const int Hp, const int Sp, const int Cin, const int halo,
     const long long total) {
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long stride = (long long)gridDim.x * blockDim.x;
@@ -110,13 +112,13 @@ extern "C" __global__ void pad_stem7_kernel(
     const long long rest = i / Sp;
     const int hp = (int)(rest % Hp);
     const long long n = rest / Hp;
-    const int h = hp - 3;
+    const int h = hp - halo;
     uint4 raw = {0, 0, 0, 0};
     ushort* u = reinterpret_cast<ushort*>(&raw);
     if (h >= 0 && h < H) {
 #pragma unroll
       for (int px = 0; px < 2; ++px) {
-        const int w = 2 * s + px - 3;
+        const int w = 2 * s + px - halo;
         if (w >= 0 && w < W) {
           const bf16* src = x + ((n * H + h) * W + w) * Cin;
 #pragma unroll
@@ -266,14 +268,20 @@ __global__ __launch_bounds__(256, 2) void conv7x7s2_kernel(
   }
 }
 
+extern "C" void launch_pad_c4(const void* x, void* xp, int Nimg, int H, int W,
+                              int Cin, int halo, int Hp, int Sp,
+                              hipStream_t s) {
+  const long long total = (long long)Nimg * Hp * Sp;
+  hipLaunchKernelGGL(pad_stem7_kernel, dim3(elementwise_grid(total, 256)),
+                     dim3(256), 0, s, (const bf16*)x, (bf16*)xp, H, W, Hp, Sp,
+                     Cin, halo, total);
+}
+
 extern "C" void launch_pad_stem7(const void* x, void* xp, int Nimg, int H,
                                  int W, int Cin, hipStream_t s) {
   const int Hp = 2 * ((H - 1) / 2 + 1) + 5;
   const int Sp = (W - 1) / 2 + 1 + 3;  // Wp / 2
-  const long long total = (long long)Nimg * Hp * Sp;
-  hipLaunchKernelGGL(pad_stem7_kernel, dim3(elementwise_grid(total, 256)),
-                     dim3(256), 0, s, (const bf16*)x, (bf16*)xp, H, W, Hp, Sp,
-                     Cin, total);
+  launch_pad_c4(x, xp, Nimg, H, W, Cin, 3, Hp, Sp, s);
 }
 
 extern "C" int conv7x7s2_tiles(int Nimg, int H, int W) {

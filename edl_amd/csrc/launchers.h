@@ -230,6 +230,10 @@ void launch_conv3x3s2_dgrad_grouped(const void* dyp, const void* wcat_g,
 // N*Hp*Wp*4 < 2^31 is the caller's to check
 void launch_pad_stem7(const void* x, void* xp, int Nimg, int H, int W,
                       int Cin, hipStream_t s);
+// the same kernel for any zero border: halo pixels above and to the left,
+// xp [N, Hp, Sp slots of 2 pixels x 4 channels], every slot written
+void launch_pad_c4(const void* x, void* xp, int Nimg, int H, int W, int Cin,
+                   int halo, int Hp, int Sp, hipStream_t s);
 int conv7x7s2_tiles(int Nimg, int H, int W);         // 16x16 output tiles
 int conv7x7s2_grid(int tiles, int max_blocks);       // persistent blocks
 // w7 [64, 224] bf16 (k = ky*32 + kx*4 + c), y [N*Ho*Wo, 64] bf16; max_blocks
@@ -251,6 +255,22 @@ int conv7x7s2_wgrad_grid(int tiles, int max_blocks);
 void launch_conv7x7s2_wgrad(const void* xp, const void* dy, float* part,
                             float* dw, int Nimg, int H, int W, int Cin,
                             int max_blocks, hipStream_t s);
+
+// ---- conv3x3_small_wgrad.hip ---- (weight gradient of the small-channel
+// 3x3 pad-1 stem convs in two classes: narrow = Cin <= 4, stride 2, xp
+// [N, 2Ho+1, 2Wo+2, 4] from launch_pad_c4 with halo 1; wide = Cin 32,
+// stride 1, xp [N, Ho+2, Wo+2, 32] from launch_pad_nhwc; Cout 32 or 64.
+// Ho, Wo are the OUTPUT extents; the class follows from stride)
+int conv3x3_small_wgrad_tiles(int Nimg, int Ho, int Wo);  // 16x16 tiles
+// persistent blocks = rows of `part` (max_blocks 0 = the default cap)
+int conv3x3_small_wgrad_grid(int tiles, int max_blocks);
+// dy [N*Ho*Wo, Cout] bf16, part fp32 [grid, Cout*48 (narrow) | Cout*288
+// (wide)] (every row written), dw fp32 [Cout, Cin, 3, 3]; two launches: the
+// partial kernel, then the fixed-order fold. xp must stay below 2^31 elements
+void launch_conv3x3_small_wgrad(const void* xp, const void* dy, float* part,
+                                float* dw, int Nimg, int Ho, int Wo, int Cin,
+                                int Cout, int stride, int max_blocks,
+                                hipStream_t s);
 
 // ---- gemm_tn.hip ---- (3x3: Cout, Cin, M, then Ho, Wo, Hp, Wp; the small
 // launcher puts CinP BEFORE stride, the others end stride, splitk, perm)

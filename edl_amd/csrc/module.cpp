@@ -1857,6 +1857,67 @@ torch::Tensor conv7x7s2_wgrad(torch::Tensor x, torch::Tensor dy2d,
   return dw;
 }
 
+// Weight gradient of the small-channel 3x3 pad-1 stem convs
+// (conv3x3_small_wgrad.hip): x [N, Cin, H, W] channels_last bf16 as
+// conv3x3_small_fwd takes it, dy2d [N*Ho*Wo, Cout] bf16 -> dW fp32
+// [Cout, Cin, 3, 3]. Two classes only: Cin <= 4 with stride 2, Cin 32 with
+// stride 1; Cout 32 or 64. x is padded here; the partial rows live for this
+// call only.
+torch::Tensor conv3x3_small_wgrad(torch::Tensor x, torch::Tensor dy2d,
+                                  int64_t stride, int64_t max_blocks) {
+  const char* who = "conv3x3_small_wgrad";
+  TORCH_CHECK(x.is_cuda() && x.dim() == 4, who, ": x 4-D GPU tensor required");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, who, ": x bf16 only");
+  TORCH_CHECK(x.is_contiguous(torch::MemoryFormat::ChannelsLast), who,
+              ": x channels_last required");
+  const int64_t N = x.size(0), Cin = x.size(1), H = x.size(2), W = x.size(3);
+  const bool narrow = Cin >= 1 && Cin <= 4 && stride == 2;
+  const bool wide = Cin == 32 && stride == 1;
+  TORCH_CHECK(narrow || wide, who, ": (Cin, stride) must be (<= 4, 2) or ",
+              "(32, 1), got (", Cin, ", ", stride, ")");
+  TORCH_CHECK(H >= 1 && W >= 1, who, ": H, W >= 1 required");
+  TORCH_CHECK(dy2d.scalar_type() == torch::kBFloat16, who, ": dy2d bf16 only");
+  TORCH_CHECK(dy2d.is_cuda() && dy2d.device() == x.device(), who,
+              ": dy2d on another device than x");
+  TORCH_CHECK(dy2d.dim() == 2, who, ": dy2d [N*Ho*Wo, Cout] required");
+  const int64_t Cout = dy2d.size(1);
+  TORCH_CHECK(Cout == 32 || Cout == 64, who, ": Cout 32 or 64 required, dy2d ",
+              "has ", Cout, " columns");
+  const int64_t Ho = out_extent(H, stride), Wo = out_extent(W, stride);
+  TORCH_CHECK(dy2d.size(0) == N * Ho * Wo, who, ": dy2d has ", dy2d.size(0),
+              " rows, x gives ", N * Ho * Wo);
+  TORCH_CHECK(dy2d.is_contiguous(), who, ": dy2d not contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dy2d.data_ptr()) % 16 == 0, who,
+              ": dy2d base not 16-byte aligned");
+  TORCH_CHECK(max_blocks >= 0, who, ": max_blocks >= 0");
+  const int64_t Hp = narrow ? 2 * Ho + 1 : H + 2;
+  const int64_t Wp = narrow ? 2 * Wo + 2 : W + 2;
+  TORCH_CHECK(N * Hp * Wp * (narrow ? 4 : 32) < (1LL << 31), who,
+              ": padded x must stay below 2^31 elements");
+  const auto f32 = x.options().dtype(torch::kFloat32);
+  auto dw = torch::empty({Cout, Cin, 3, 3}, f32);
+  const int mb = (int)std::min<int64_t>(max_blocks, 1 << 20);
+  const int rows = conv3x3_small_wgrad_grid(
+      conv3x3_small_wgrad_tiles((int)N, (int)Ho, (int)Wo), mb);
+  auto s = cur_stream();
+  auto part = torch::empty({rows, Cout * (narrow ? 48 : 288)}, f32);
+  torch::Tensor xp;
+  if (N == 0) {
+    xp = torch::empty({0}, x.options());
+  } else if (narrow) {
+    xp = torch::empty({N, Hp, Wp, 4}, x.options());
+    launch_pad_c4(x.data_ptr(), xp.data_ptr(), (int)N, (int)H, (int)W,
+                  (int)Cin, 1, (int)Hp, (int)(Wp / 2), s);
+  } else {
+    xp = pad_nhwc_flat(x, 32, s);
+  }
+  launch_conv3x3_small_wgrad(xp.data_ptr(), dy2d.data_ptr(),
+                             part.data_ptr<float>(), dw.data_ptr<float>(),
+                             (int)N, (int)Ho, (int)Wo, (int)Cin, (int)Cout,
+                             (int)stride, mb, s);
+  return dw;
+}
+
 // the unpadded twins: x 4-D channels_last bf16 [N, C, H, W], padded here
 torch::Tensor conv3x3_fwd(torch::Tensor x, torch::Tensor w3, int64_t stride) {
   check_nhwc_bf16(x, "conv3x3", 64);
@@ -2139,6 +2200,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "weight gradient of the 7x7 stride-2 stem conv: x as conv7x7s2_fwd "
         "takes it, dy2d [N*Ho*Wo, 64] bf16 -> fp32 [64, Cin, 7, 7]; "
         "max_blocks caps the persistent grid (0 = default)");
+  m.def("conv3x3_small_wgrad", &conv3x3_small_wgrad, py::arg("x"),
+        py::arg("dy2d"), py::arg("stride"), py::arg("max_blocks") = 0,
+        "weight gradient of the small-channel 3x3 pad-1 stem convs, (Cin, "
+        "stride) = (<= 4, 2) or (32, 1), Cout 32 or 64: x as "
+        "conv3x3_small_fwd takes it, dy2d [N*Ho*Wo, Cout] bf16 -> fp32 "
+        "[Cout, Cin, 3, 3]; max_blocks caps the persistent grid (0 = default)");
   m.def("transpose_pad", &transpose_pad,
         "bf16 [M,C] -> [C, ceil64(M)] transpose with zero pad");
   m.def("gemm_bt_splitk", &gemm_bt_splitk,

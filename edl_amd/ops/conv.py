@@ -6,9 +6,11 @@ ROCm), which runs far closer to the MFMA roofline than MIOpen's igemm
 path at these shapes (igemm measured ~2-4% of bf16 peak at bs32, by
 rocprof). 3x3 same-pad convolutions run the in-repo implicit-GEMM kernels
 (dense C % 64, small-channel stem, grouped ResNeXt shapes — forward and
-backward), and the 7x7 stride-2 stem of the ResNeXt teacher (Cin <= 4 -> 64)
-runs its forward and its weight gradient on the in-repo conv7x7 kernels;
-everything else stays on F.conv2d (MIOpen).
+backward; the three ResNet-vd stem shapes take their weight gradient from
+conv3x3_small_wgrad.hip, other small shapes from the library), and the 7x7
+stride-2 stem of the ResNeXt teacher (Cin <= 4 -> 64) runs its forward and
+its weight gradient on the in-repo conv7x7 kernels; everything else stays on
+F.conv2d (MIOpen).
 
 Weight layout stays nn.Conv2d-compatible ([Cout, Cin, kh, kw]) so state
 dicts interchange."""
@@ -352,12 +354,25 @@ def _repack_w3_small(weight, cpt):
     return out.reshape(64, taps_pad * cpt).contiguous()
 
 
+# Default of EDL_STEM_WGRAD (read per backward). hip: on each of the three
+# ResNet50_vd stem shapes at batch 32 the slowest of its 9 windows is below
+# the library's fastest (docs/kernels.md, "wgrad: conv3x3_small_wgrad.hip").
+_STEM_WGRAD_DEFAULT = "hip"
+
+
+def _stem_wgrad_hip_class(ci, co, stride):
+    """The shapes conv3x3_small_wgrad.hip serves: narrow (Cin <= 4, stride
+    2) and wide (Cin 32, stride 1), Cout 32 or 64."""
+    return co in (32, 64) and ((ci <= 4 and stride == 2)
+                               or (ci == 32 and stride == 1))
+
+
 class _Conv3x3SmallHip(torch.autograd.Function):
     """Deep-stem 3x3 conv (Cin in {3..64}, Cout <= 64) on the small-channel
     implicit-GEMM kernel: fwd + dgrad in-repo (replaces MIOpen's stem
-    igemm/naive kernels and their find phase — VERDICT r1 #4); wgrad runs
-    as ONE plain library GEMM on an unfold im2col (hipBLASLt — a plain
-    GEMM per the north star's library-GEMM allowance)."""
+    igemm/naive kernels and their find phase — VERDICT r1 #4); wgrad per
+    EDL_STEM_WGRAD (see backward): conv3x3_small_wgrad.hip for the ResNet-vd
+    stem shapes, torch.nn.grad.conv2d_weight for the others."""
 
     @staticmethod
     def forward(ctx, x, w_param, w3s, w3srot, stride, cout, part_out=None):
@@ -390,13 +405,20 @@ class _Conv3x3SmallHip(torch.autograd.Function):
             cpt = _small_cpt(co)
             dx2d = ext().conv3x3_small_fwd(dyb, ctx.w3srot, ci, cpt, 1)
             dx = _nchw_view(dx2d, n, h, w)
-        # wgrad. Default: torch.nn.grad.conv2d_weight (MIOpen igemm_wrw,
+        # wgrad. EDL_STEM_WGRAD: hip = conv3x3_small_wgrad.hip for the two
+        # shape classes it is written for (_stem_wgrad_hip_class: the three
+        # ResNetVd stem convs), any other small shape keeps the library
+        # line; miopen = torch.nn.grad.conv2d_weight (MIOpen igemm_wrw,
         # ~51 us/call steady). The unfold+hipBLASLt route is kept opt-in
         # (EDL_STEM_WGRAD=unfold) but MEASURED NEGATIVE: hipBLASLt runs
         # the [32, 401k] @ [401k, 288] reduction GEMM at ~918 us — no
         # split-K pick at tiny M,N (gpurun_out/r2c7, bench 3221 -> 2566).
-        route = os.environ.get("EDL_STEM_WGRAD", "miopen")
-        if route == "tn":
+        route = os.environ.get("EDL_STEM_WGRAD", _STEM_WGRAD_DEFAULT)
+        if (route == "hip" and dyb.is_cuda
+                and _stem_wgrad_hip_class(ci, co, ctx.stride)):
+            dw = ext().conv3x3_small_wgrad(
+                x, dyb.permute(0, 2, 3, 1).reshape(-1, co), ctx.stride)
+        elif route == "tn":
             # in-repo G3S gather wgrad (gemm_tn3x3_small): dY cols padded
             # to 64, x channel-padded to pow2 inside the binding; output
             # [64, N2v] sliced back to [co, ci, 3, 3]

@@ -6,6 +6,7 @@ conv1x1 shapes at bs32. Run on a GPU box:
     python tools/gemm_bench.py --grouped-bwd # grouped 3x3 dgrad/wgrad vs MIOpen
     python tools/gemm_bench.py --stem7       # 7x7/s2 stem conv vs MIOpen
     python tools/gemm_bench.py --stem7-wgrad # its weight gradient vs MIOpen
+    python tools/gemm_bench.py --stem3-wgrad # the 3x3 deep-stem wgrads vs MIOpen
 """
 import os
 import sys
@@ -440,8 +441,64 @@ def main_stem7_wgrad(windows=9, l3_bytes=256 << 20, max_sets=64):
         torch.cuda.empty_cache()
 
 
+# (N, Cin, Cout, H, W, stride) of the three ResNet50_vd deep-stem convs at the
+# benchmark's batch
+STEM3_SHAPES = [(32, 3, 32, 224, 224, 2), (32, 32, 32, 112, 112, 1),
+                (32, 32, 64, 112, 112, 1)]
+
+
+def main_stem3_wgrad(windows=9, l3_bytes=256 << 20, max_sets=64):
+    """3x3 deep-stem weight gradient per conv: (a)
+    torch.nn.grad.conv2d_weight on channels_last bf16 after its find phase,
+    (b) conv3x3_small_wgrad (pad launch and fold included) at the default
+    grid cap, then (b) at each max_blocks of STEM7_WGRAD_BLOCKS. Columns and
+    cold operands as --stem7-wgrad. GB/s of (b): x + dY read once, over its
+    median. The last line applies the rule for the default of
+    EDL_STEM_WGRAD: max of (b) below min of (a) on every shape."""
+    e = ops.ext()
+    cl = torch.channels_last
+    keys = ["a", "b"] + ["b@%d" % mb for mb in STEM7_WGRAD_BLOCKS]
+    print(("%-26s" + " %-26s" * len(keys) + " %8s") % (
+        "(N,Cin,Cout,H,W,s)", "(a) library", "(b) conv3x3_small_wgrad",
+        *["(b) max_blocks %d" % mb for mb in STEM7_WGRAD_BLOCKS], "(b) GB/s"))
+    wins = []
+    for shape in STEM3_SHAPES:
+        n, ci, co, h, wd, st = shape
+        ho, wo = (h - 1) // st + 1, (wd - 1) // st + 1
+        read_bytes = 2 * n * (ci * h * wd + co * ho * wo)
+        nsets = min(max_sets, max(2, -(-int(1.25 * l3_bytes) // read_bytes)))
+        sets = [(torch.randn(n, ci, h, wd, device="cuda").to(
+            torch.bfloat16).contiguous(memory_format=cl),
+            torch.randn(n, co, ho, wo, device="cuda").to(
+            torch.bfloat16).contiguous(memory_format=cl))
+            for _ in range(nsets)]
+
+        def hip(mb):
+            return lambda x, dy: e.conv3x3_small_wgrad(
+                x, dy.permute(0, 2, 3, 1).reshape(-1, co), st, mb)
+
+        fns = {"a": lambda x, dy: torch.nn.grad.conv2d_weight(
+            x, (co, ci, 3, 3), dy, stride=(st, st), padding=(1, 1)),
+            "b": hip(0)}
+        for mb in STEM7_WGRAD_BLOCKS:
+            fns["b@%d" % mb] = hip(mb)
+        us = _graph_us_alternating(fns, sets, windows)
+        cols = ["%8.1f [%7.1f..%7.1f]" % (u[len(u) // 2], u[0], u[-1])
+                for u in (us[k] for k in keys)]
+        med_b = us["b"][len(us["b"]) // 2]
+        print(("%-26s" + " %-26s" * len(keys) + " %8.0f") % (
+            str(shape), *cols, read_bytes / med_b / 1e3), flush=True)
+        wins.append(us["b"][-1] < us["a"][0])
+        del sets
+        torch.cuda.empty_cache()
+    print("rule (max (b) < min (a)) per shape: %s -> default %s" % (
+        wins, "hip" if all(wins) else "miopen"))
+
+
 if __name__ == "__main__":
-    if "--stem7-wgrad" in sys.argv:
+    if "--stem3-wgrad" in sys.argv:
+        main_stem3_wgrad()
+    elif "--stem7-wgrad" in sys.argv:
         main_stem7_wgrad()
     elif "--stem7" in sys.argv:
         main_stem7()
