@@ -18,7 +18,7 @@
 // Built without packed-fp32 VALU ops (build_hip.py): the folds are plain
 // v_add_f32 chains, which is also what the generated code is read against
 // in docs/kernels.md.
-#include "common.h"
+#include "bn_phases.h"
 #include "launchers.h"
 
 constexpr int kFinThreads = 1024;
@@ -130,20 +130,9 @@ extern "C" __global__ __launch_bounds__(kFinThreads) void bn_finalize_kernel(
   if (!fin) return;
   const float ssum = fin_fold(accs, lane);
   const float qsum = fin_fold(accq, lane);
-  const float inv_m = 1.0f / (float)M;
-  const float mean = ssum * inv_m;
-  const float var = fmaxf(qsum * inv_m - mean * mean, 0.0f);
-  const float invstd = rsqrtf(var + eps);
-  mean_out[c] = mean;
-  invstd_out[c] = invstd;
-  scale_out[c] = g * invstd;
-  shift_out[c] = bt - g * invstd * mean;
-  if (running_mean != nullptr) {
-    // unbiased variance for the running estimate (torch semantics)
-    const float ub = (M > 1) ? var * (float)M / (float)(M - 1) : var;
-    running_mean[c] = fmaf(momentum, mean - rm, rm);
-    running_var[c] = fmaf(momentum, ub - rv, rv);
-  }
+  bn_channel_finalize(ssum, qsum, g, bt, rm, rv, M, momentum, eps, c, mean_out,
+                      invstd_out, scale_out, shift_out, running_mean,
+                      running_var);
 }
 
 extern "C" void launch_bn_finalize(float* partial, int nblocks, int zero_src,

@@ -9,39 +9,19 @@
 // folded in, dgamma/dbeta written straight into fp32 grad bucket views.
 //
 // Layout: x is NHWC [M rows, C channels], C % 8 == 0; the training kernels
-// additionally need C a power of two <= 2048 (all ResNet/ResNeXt widths;
-// see row_partition). Each thread owns 8 consecutive channels (one
-// ushort4x2 = 16 B load, guide G13); a block's 256 threads cover 2048
-// channels' worth of a row-group; blocks grid-stride over rows, fold
-// per-channel fp32 partials in LDS and store one partial row per block.
-#include <type_traits>
-
-#include "common.h"
+// additionally need C a power of two <= 2048 (see row_partition: every
+// ResNet width, and ResNeXt up to 2048; the 4096-wide stage-4 BNs of
+// ResNeXt101_32x16d train through bn_wide.hip). Each thread owns 8
+// consecutive channels (one ushort4x2 = 16 B load, guide G13); a block's
+// 256 threads cover 2048 channels' worth of a row-group; blocks grid-stride
+// over rows, fold per-channel fp32 partials in LDS and store one partial
+// row per block.
+#include "bn_phases.h"
 #include "launchers.h"
 
-using bf16 = __hip_bfloat16;
-
-struct F8 {
-  float v[8];
-};
-
-__device__ __forceinline__ F8 load8(const bf16* p) {
-  // 16-byte vector load of 8 bf16. assume_aligned is LOAD-BEARING: from
-  // bf16 pointer arithmetic LLVM infers align 2 and lowers the uint4
-  // load as ushort+dwordx2+dword+ushort pieces (4 VMEM ops, seen in the
-  // .s of the r2 reduce loop — the BN kernels ran 5x off roofline).
-  const uint4 raw = *reinterpret_cast<const uint4*>(
-      __builtin_assume_aligned(p, 16));
-  F8 o;
-  const ushort* u = reinterpret_cast<const ushort*>(&raw);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    union { unsigned u32; float f; } c;
-    c.u32 = ((unsigned)u[i]) << 16;
-    o.v[i] = c.f;
-  }
-  return o;
-}
+// F8, load8, store8 and the per-octet math (relu_select, apply_octet,
+// dx_octet) and dispatch_bools live in bn_phases.h: bn_wide.hip runs the
+// same pieces.
 
 // load8 whose 16-byte load stays ONE dwordx4: where the consumer masks
 // single elements (the ReLU select in the dx kernels) LLVM narrows the
@@ -61,28 +41,12 @@ __device__ __forceinline__ F8 load8_whole(const bf16* p) {
   return o;
 }
 
-__device__ __forceinline__ void store8(bf16* p, const F8& x) {
-  uint4 raw;
-  ushort* u = reinterpret_cast<ushort*>(&raw);
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    u[i] = (ushort)(__hip_bfloat16_raw(__float2bfloat16(x.v[i])).x);
-  }
-  *reinterpret_cast<uint4*>(__builtin_assume_aligned(p, 16)) = raw;
-}
-
 // ---------------- shared phases ----------------
 // Each piece below is the single copy of a step that several kernels run.
 // Those that stride by the block size take it as `nthr`: the kernels read
 // blockDim.x and pass it down, because read inside a device function it
 // misses the compiler's uniform-work-group fold (a vector load and a
 // select per kernel instead of one scalar load).
-
-// dy_eff: keep g[k] where bit k of the fwd apply's mask byte is set.
-__device__ __forceinline__ void relu_select(F8& g, const unsigned mb) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) g.v[k] = (mb >> k) & 1 ? g.v[k] : 0.0f;
-}
 
 // Flat octet index over [rows, C/8] -> (channel octet, row). Every model
 // width is pow2: % and / as mask and shift (the generic 64-bit divmod
@@ -204,31 +168,6 @@ __global__ void bn_stats_kernel(
 
 // K2: the fwd finalize (partials -> mean/invstd/scale/shift, running stats)
 // lives in bn_finalize.hip.
-
-// One octet of the fwd apply: v = relu?(v*scale + shift [+ res]). Returns
-// the ReLU mask byte (bit k = channel c0+k positive), 0 without RELU.
-// `res` points at this octet's residual and is read only with ADD.
-template <bool RELU, bool ADD>
-__device__ __forceinline__ unsigned char apply_octet(
-    F8& v, const bf16* res, const float* __restrict__ scale,
-    const float* __restrict__ shift, const int c0) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) v.v[k] = fmaf(v.v[k], scale[c0 + k], shift[c0 + k]);
-  if (ADD) {
-    F8 rv = load8(res);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v.v[k] += rv.v[k];
-  }
-  unsigned char mb = 0;
-  if (RELU) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      if (v.v[k] > 0.0f) mb |= (1u << k);
-      v.v[k] = fmaxf(v.v[k], 0.0f);
-    }
-  }
-  return mb;
-}
 
 // K3: y = relu?(x*scale + shift [+ res]); NHWC vectorized by channel octets.
 // MASK (with RELU only): also emit a 1-bit-per-channel ReLU mask (one byte
@@ -431,31 +370,6 @@ extern "C" __global__ void bn_bwd_finalize_kernel(
 
 // (no separate dgamma/dbeta kernel: the bwd-reduce workspace IS [dbeta; dgamma]
 // — sums[0:C] = s1 = dbeta, sums[C:2C] = s2 = dgamma; Python returns views.)
-
-// One octet of dx = scale * (dy_eff - s1/M - xhat * s2/M) (TRAINING), or
-// scale * dy_eff with frozen stats. g is dy_eff: loaded and masked by the
-// caller, each kernel with its own load helper.
-template <bool TRAINING>
-__device__ __forceinline__ F8 dx_octet(
-    const F8& g, const F8& xv, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ gamma,
-    const float* __restrict__ sums, const float inv_m, const int c0,
-    const int C) {
-  F8 o;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int c = c0 + k;
-    const float is = invstd[c];
-    if (TRAINING) {
-      const float xhat = (xv.v[k] - mean[c]) * is;
-      o.v[k] = gamma[c] * is *
-               (g.v[k] - sums[c] * inv_m - xhat * sums[C + c] * inv_m);
-    } else {
-      o.v[k] = gamma[c] * is * g.v[k];
-    }
-  }
-  return o;
-}
 
 // B3: dx (+ dres) as its own launch.
 template <bool RELU, bool ADD, bool TRAINING>
@@ -664,23 +578,6 @@ extern "C" int bn_bwd_grid(long long M, int C) {
   return bn_grid_common(M, C,
                         env_ll("EDL_BN_BWD_GRID_CAP",
                                env_ll("EDL_BN_GRID_CAP", 192)));
-}
-
-// Runtime bools -> template arguments: calls f with one std::true_type or
-// std::false_type per bool, e.g.
-//   dispatch_bools([&](auto R, auto A) { kernel<decltype(R)::value, ...> },
-//                  relu, add);
-template <class F>
-static void dispatch_bools(F&& f) {
-  f();
-}
-
-template <class F, class... Bools>
-static void dispatch_bools(F&& f, const bool b, const Bools... rest) {
-  if (b)
-    dispatch_bools([&](auto... t) { f(std::true_type{}, t...); }, rest...);
-  else
-    dispatch_bools([&](auto... t) { f(std::false_type{}, t...); }, rest...);
 }
 
 extern "C" void launch_bn_stats(const void* x, float* partial, int grid,

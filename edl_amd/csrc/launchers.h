@@ -168,6 +168,22 @@ void launch_bn_bwd_fused(const void* dy, const unsigned char* mask,
                          int grid, int nfin, long long M, int C, bool relu,
                          bool add, hipStream_t s);
 
+// ---- bn_wide.hip ---- (C > 2048, C % 64 == 0, 2 <= M; one launch a pass;
+// mask null without relu; sums = [dbeta; dgamma], accumulators as above)
+// largest M served from the LDS-resident slab at the slab width the
+// launcher picks for C (0: none)
+int bn_wide_resident_rows(int C, int backward);
+void launch_bn_wide_fwd(const void* x, void* y, unsigned char* mask,
+                        const float* gamma, const float* beta, float* mean,
+                        float* invstd, float* rmean, float* rvar,
+                        float momentum, float eps, int M, int C, bool relu,
+                        hipStream_t s);
+void launch_bn_wide_bwd(const void* dy, const unsigned char* mask,
+                        const void* x, const float* mean,
+                        const float* invstd, const float* gamma, float* sums,
+                        float* db_acc, float* dg_acc, void* dx, int M, int C,
+                        bool relu, hipStream_t s);
+
 // ---- gemm_bt.hip ---- (M, N, K: C[M,N] = A[M,K] @ B[N,K]^T)
 int gemm_bt_tiles_m(int M, int N);
 void launch_gemm_bt(const void* A, const void* B, void* C, int M, int N,

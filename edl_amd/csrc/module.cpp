@@ -1,5 +1,6 @@
 // Python bindings for the edl_amd CDNA4 kernel layer (edl_amd._C).
 // Compiled by hipcc directly (no hipify, no CUDA path) — see build_hip.py.
+#include <climits>
 #include <iterator>
 #include <mutex>
 #include <unordered_map>
@@ -984,6 +985,105 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
   }
   // dbeta = sums[0], dgamma = sums[1] (views of the reduce workspace)
   return {dx, sums[1], sums[0], dres};
+}
+
+// ---- bn_wide.hip: training BN(+ReLU) at C > 2048, one launch a pass ----
+// The kernels index by (row, channel slab) without a bounds test, so every
+// pointer they take is checked here for dtype, size, layout and device.
+static void check_bn_wide_x(const torch::Tensor& x, const torch::Tensor& gamma,
+                            const char* who) {
+  const int64_t C = gamma.numel();
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16 &&
+                  x.device() == gamma.device(),
+              who, ": x must be a bf16 tensor on gamma's GPU");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == C && x.is_contiguous(), who,
+              ": x must be a contiguous [M, C] view");
+  TORCH_CHECK(C > 2048 && C % 64 == 0, who,
+              ": C > 2048 and C % 64 == 0 required (bn_fwd_train / bn_bwd "
+              "serve the narrower widths), got ", C);
+  TORCH_CHECK(x.size(0) >= 2 && x.size(0) <= INT_MAX, who,
+              ": 2 <= M < 2^31 rows required, got ", x.size(0));
+}
+
+static void check_bn_wide_vec(const torch::Tensor& v, const torch::Tensor& x,
+                              const char* who, const char* name) {
+  TORCH_CHECK(v.defined() && v.scalar_type() == torch::kFloat32 &&
+                  v.numel() == x.size(1) && v.is_contiguous() &&
+                  v.device() == x.device(),
+              who, ": ", name, " must be fp32 [C], contiguous, on x's GPU");
+}
+
+std::vector<torch::Tensor> bn_wide_fwd_train(torch::Tensor x,
+                                             torch::Tensor gamma,
+                                             torch::Tensor beta,
+                                             torch::Tensor rmean,
+                                             torch::Tensor rvar,
+                                             double momentum, double eps,
+                                             bool relu) {
+  const char* who = "bn_wide_fwd_train";
+  check_bn_wide_x(x, gamma, who);
+  check_bn_wide_vec(gamma, x, who, "gamma");
+  check_bn_wide_vec(beta, x, who, "beta");
+  TORCH_CHECK(rmean.defined() == rvar.defined(), who,
+              ": running_mean and running_var come together");
+  if (rmean.defined()) {
+    check_bn_wide_vec(rmean, x, who, "running_mean");
+    check_bn_wide_vec(rvar, x, who, "running_var");
+  }
+  const int64_t M = x.size(0), C = x.size(1);
+  auto opts = gamma.options();
+  auto mean = torch::empty({C}, opts);
+  auto invstd = torch::empty({C}, opts);
+  auto y = torch::empty_like(x);
+  auto msk = relu ? torch::empty({M, C / 8}, x.options().dtype(torch::kUInt8))
+                  : torch::empty({0}, x.options().dtype(torch::kUInt8));
+  launch_bn_wide_fwd(x.data_ptr(), y.data_ptr(),
+                     relu ? (unsigned char*)msk.data_ptr() : nullptr,
+                     gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                     mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                     rmean.defined() ? rmean.data_ptr<float>() : nullptr,
+                     rvar.defined() ? rvar.data_ptr<float>() : nullptr,
+                     (float)momentum, (float)eps, (int)M, (int)C, relu,
+                     cur_stream());
+  return {y, mean, invstd, msk};
+}
+
+std::vector<torch::Tensor> bn_wide_bwd(torch::Tensor dy,
+                                       c10::optional<torch::Tensor> msk,
+                                       torch::Tensor x, torch::Tensor mean,
+                                       torch::Tensor invstd,
+                                       torch::Tensor gamma, bool relu,
+                                       c10::optional<torch::Tensor> dgamma_acc,
+                                       c10::optional<torch::Tensor> dbeta_acc) {
+  const char* who = "bn_wide_bwd";
+  check_bn_wide_x(x, gamma, who);
+  check_bn_wide_vec(gamma, x, who, "gamma");
+  check_bn_wide_vec(mean, x, who, "mean");
+  check_bn_wide_vec(invstd, x, who, "invstd");
+  const int64_t M = x.size(0), C = x.size(1);
+  TORCH_CHECK(dy.scalar_type() == torch::kBFloat16 &&
+                  dy.device() == x.device() && dy.sizes() == x.sizes(),
+              who, ": dy must be bf16 [M, C] on x's GPU");
+  TORCH_CHECK(!relu || (msk.has_value() && msk->numel() == M * (C / 8) &&
+                        msk->scalar_type() == torch::kUInt8 &&
+                        msk->is_contiguous() && msk->device() == x.device()),
+              who, ": relu path needs the fwd mask, uint8 [M, C/8]");
+  float* dg_acc = acc_ptr(dgamma_acc, C, "bn_wide_bwd: dgamma_acc fp32 [C]");
+  float* db_acc = acc_ptr(dbeta_acc, C, "bn_wide_bwd: dbeta_acc fp32 [C]");
+  TORCH_CHECK((!dgamma_acc.has_value() || dgamma_acc->device() == x.device()) &&
+                  (!dbeta_acc.has_value() || dbeta_acc->device() == x.device()),
+              who, ": accumulators must be on x's GPU");
+  auto dyc = dy.is_contiguous() ? dy : dy.contiguous();
+  auto sums = torch::empty({2, C}, gamma.options());
+  auto dx = torch::empty_like(x);
+  launch_bn_wide_bwd(dyc.data_ptr(),
+                     relu ? (const unsigned char*)msk->data_ptr() : nullptr,
+                     x.data_ptr(), mean.data_ptr<float>(),
+                     invstd.data_ptr<float>(), gamma.data_ptr<float>(),
+                     sums.data_ptr<float>(), db_acc, dg_acc, dx.data_ptr(),
+                     (int)M, (int)C, relu, cur_stream());
+  // dbeta = sums[0], dgamma = sums[1], as bn_bwd returns them
+  return {dx, sums[1], sums[0]};
 }
 
 // C[M, N] = A[M, K] @ B[N, K]^T, bf16 row-major -> {C} or, with_stats,
@@ -2135,6 +2235,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("invstd"), py::arg("gamma"), py::arg("relu"), py::arg("add"),
         py::arg("training"), py::arg("dgamma_acc") = py::none(),
         py::arg("dbeta_acc") = py::none(), py::arg("pad_hw") = py::none());
+  m.def("bn_wide_fwd_train", &bn_wide_fwd_train,
+        "training BN(+ReLU) fwd at C > 2048, C % 64 == 0, one launch -> "
+        "(y, mean, invstd, mask)",
+        py::arg("x"), py::arg("gamma"), py::arg("beta"), py::arg("rmean"),
+        py::arg("rvar"), py::arg("momentum"), py::arg("eps"),
+        py::arg("relu"));
+  m.def("bn_wide_bwd", &bn_wide_bwd,
+        "training BN(+ReLU) bwd at C > 2048, one launch -> "
+        "(dx, dgamma, dbeta)",
+        py::arg("dy"), py::arg("msk"), py::arg("x"), py::arg("mean"),
+        py::arg("invstd"), py::arg("gamma"), py::arg("relu"),
+        py::arg("dgamma_acc") = py::none(), py::arg("dbeta_acc") = py::none());
+  m.def("bn_wide_resident_rows", &bn_wide_resident_rows,
+        "largest M bn_wide serves from its LDS-resident slab (0: none)",
+        py::arg("C"), py::arg("backward"));
   m.def("pad_nhwc", &pad_nhwc,
         "channels_last bf16 [N,C,H,W] -> zero-halo padded [N,H+2,W+2,C]");
   m.def("conv3x3_fwd_padded", &conv3x3_fwd_padded,

@@ -43,10 +43,19 @@ class _FusedBN(torch.autograd.Function):
         ctx.shape4 = tuple(x.shape) if x.dim() == 4 else None
         x2d = _to_2d(x) if x.dim() == 4 else x
         assert ctx.shape4 is not None or (pad_out is None and dx_pad is None)
-        y, mean, invstd, mask = ext().bn_fwd_train(
-            x2d, gamma, beta, rmean, rvar, momentum, eps, res2d, relu,
-            pre_part, ctx.shape4[2:] if pad_out is not None else None
-        )
+        if x2d.shape[1] > 2048:
+            # bn_wide.hip: one launch, statistics from x itself; no residual
+            # and no padded hand-off at these widths (_fused_applies, _fused)
+            assert res2d is None and pad_out is None and dx_pad is None
+            if pre_part is not None:
+                pre_part.zero_()  # pooled: hand it back clean (see forward)
+            y, mean, invstd, mask = ext().bn_wide_fwd_train(
+                x2d, gamma, beta, rmean, rvar, momentum, eps, relu)
+        else:
+            y, mean, invstd, mask = ext().bn_fwd_train(
+                x2d, gamma, beta, rmean, rvar, momentum, eps, res2d, relu,
+                pre_part, ctx.shape4[2:] if pad_out is not None else None
+            )
         # backward reads the 1-bit ReLU mask instead of y (16x fewer bytes)
         ctx.save_for_backward(x2d, mask, mean, invstd, gamma)
         ctx.relu = relu
@@ -64,11 +73,17 @@ class _FusedBN(torch.autograd.Function):
         x2d, mask, mean, invstd, gamma = ctx.saved_tensors
         if dy.dim() == 4:
             dy = _to_2d(dy)
-        dx, dgamma, dbeta, dres = ext().bn_bwd(
-            dy, mask, x2d, mean, invstd, gamma, ctx.relu, ctx.has_res, True,
-            ctx.dg_t, ctx.db_t,
-            ctx.shape4[2:] if ctx.dx_pad is not None else None
-        )
+        if x2d.shape[1] > 2048:
+            dx, dgamma, dbeta = ext().bn_wide_bwd(
+                dy, mask, x2d, mean, invstd, gamma, ctx.relu, ctx.dg_t,
+                ctx.db_t)
+            dres = None
+        else:
+            dx, dgamma, dbeta, dres = ext().bn_bwd(
+                dy, mask, x2d, mean, invstd, gamma, ctx.relu, ctx.has_res,
+                True, ctx.dg_t, ctx.db_t,
+                ctx.shape4[2:] if ctx.dx_pad is not None else None
+            )
         if dx.dim() == 4:  # padded [N, H+2, W+2, C]
             ctx.dx_pad[:] = [dx]
             dx = padded_interior(dx)
@@ -140,12 +155,19 @@ class BNReLU2d(nn.Module):
             return False
         wide = self.num_features > 2048
         if wide or self.num_features & (self.num_features - 1):
-            # training reduce kernels cap at 2048 (LDS) and need a pow2
-            # width (row partition); the EVAL apply kernel has neither
-            # limit — wide teachers opt in until the round-3 GPU
-            # validation (EDL_BN_WIDE_EVAL=1; see NOTES r2c42)
-            if (self.training or torch.is_grad_enabled() or
-                    (wide and os.environ.get("EDL_BN_WIDE_EVAL", "0") != "1")):
+            # the row-split training kernels (bnrelu.hip) cap at 2048 (LDS)
+            # and need a pow2 width (row partition). Above 2048 a training
+            # module runs the channel-slab kernels (bn_wide.hip: C % 64 ==
+            # 0, no residual; EDL_BN_WIDE_TRAIN=0 turns them off). The EVAL
+            # apply kernel has no width limit — wide teachers opt in until
+            # the round-3 GPU validation (EDL_BN_WIDE_EVAL=1; see NOTES
+            # r2c42)
+            if self.training or torch.is_grad_enabled():
+                if not (wide and self.training and res is None
+                        and self.num_features % 64 == 0
+                        and os.environ.get("EDL_BN_WIDE_TRAIN", "1") == "1"):
+                    return False
+            elif wide and os.environ.get("EDL_BN_WIDE_EVAL", "0") != "1":
                 return False
         if res is not None and (
             res.dtype != torch.bfloat16
@@ -169,6 +191,8 @@ class BNReLU2d(nn.Module):
         x2d = _to_2d(x)
         res2d = _to_2d(res) if res is not None else None
         if self.training:
+            if self.num_features > 2048:  # bn_wide.hip writes plain [M, C]
+                pad_out, dx_pad = False, None
             # padded-layout hand-offs to a neighbouring 3x3 conv (see
             # _FusedBN.forward); both are plain-BN(+ReLU) only
             pad_out = (pad_out and self.act and res is None
