@@ -12,10 +12,12 @@
 // additionally need C a power of two <= 2048 (see row_partition: every
 // ResNet width, and ResNeXt up to 2048; the 4096-wide stage-4 BNs of
 // ResNeXt101_32x16d train through bn_wide.hip). Each thread owns 8
-// consecutive channels (one ushort4x2 = 16 B load, guide G13); a block's
-// 256 threads cover 2048 channels' worth of a row-group; blocks grid-stride
-// over rows, fold per-channel fp32 partials in LDS and store one partial
-// row per block.
+// consecutive channels (one ushort4x2 = 16 B load, guide G13). The two
+// reductions (bn_stats, bn_bwd_reduce) run on a (row-block, channel-slab)
+// grid: a block owns 64 channels of a row subset, folds its fp32 sums
+// through shuffles and LDS in a fixed order and stores its slab of one
+// partial row (see slab_partition; EDL_BN_SLAB=0 selects the older
+// row-only partition, where a block covers all C channels).
 #include "bn_phases.h"
 #include "launchers.h"
 
@@ -125,9 +127,136 @@ __device__ __forceinline__ void fold_end(float* lsum, const float (&a)[8],
   for (int i = threadIdx.x; i < 2 * C; i += nthr) out[i] = lsum[i];
 }
 
+// ---------------- channel-slab x row partition ----------------
+// The shipped partition of the two reductions (EDL_BN_SLAB=0 keeps the
+// row-only one above). grid = (R row-blocks, S channel slabs): block (r, s)
+// owns the Cs channels [s*Cs, (s+1)*Cs) of the rows r*rpb + k*R*rpb + j,
+// j < rpb = nthr / (Cs/8). Cs = min(C, 64), so a wave still reads 128
+// contiguous bytes of a row and a wide layer spreads over S = C/64 times
+// the blocks the row-only grid gave it, each thread with 1/S of the rows:
+// the C >= 512 layers go from 32..128 blocks walking a dozen dependent load
+// rounds to about a thousand blocks with one or two.
+// PRECONDITION: C a power of two in 8..2048 (as row_partition) and nthr a
+// multiple of 64 in 256..1024, so Cs/8 <= 8 divides the wave.
+struct SlabPart {
+  long long row0, rstride;
+  int c0;   // first channel of this thread's octet, in the whole row
+  int c8s;  // octets per slab row = threads per row
+};
+
+__device__ __forceinline__ SlabPart slab_partition(const int C,
+                                                   const unsigned nthr) {
+  const int Cs = C < 64 ? C : 64;
+  SlabPart p;
+  p.c8s = Cs >> 3;
+  const int c8l = 31 - __clz((unsigned)p.c8s);  // pow2: / and % as shift, mask
+  const int rpb = (int)nthr >> c8l;
+  p.row0 = (long long)blockIdx.x * rpb + (threadIdx.x >> c8l);
+  p.rstride = (long long)gridDim.x * rpb;
+  p.c0 = blockIdx.y * Cs + (int)(threadIdx.x & (p.c8s - 1)) * 8;
+  return p;
+}
+
+// Rows r, r + rstride, ... of one 4-row round. MASKED (the last round of a
+// thread): a row past the end is read from row M - 1 instead, so the load
+// stays in bounds and the round branch-free, and `ok` zeroes what it adds.
+template <bool MASKED>
+struct Round4 {
+  long long row[4];
+  bool ok[4];
+  __device__ __forceinline__ Round4(const long long r, const long long rstride,
+                                    const long long M) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long rr = r + u * rstride;
+      ok[u] = !MASKED || rr < M;
+      row[u] = ok[u] ? rr : M - 1;
+    }
+  }
+};
+
+// Block fold of the slab kernels, free of atomics and in a fixed order:
+// lanes of a wave that own the same octet (lane bits >= log2(c8s)) fold by
+// xor shuffles, one lane per octet stores the wave's 2*Cs sums into its LDS
+// row, and thread t < 2*Cs adds the rows wave 0, 1, ... and stores column t
+// of the block's slab in partial row blockIdx.x. (The row-only fold_end
+// does 16 LDS atomics per thread; at Cs = 64 a 1024-thread block would put
+// 128 threads on every word.)
+__device__ __forceinline__ void slab_fold(float* lw, float (&a)[8],
+                                          float (&b)[8], const SlabPart& p,
+                                          const int C, const unsigned nthr,
+                                          float* __restrict__ partial) {
+  const int Cs = p.c8s * 8;
+  for (int off = 32; off >= p.c8s; off >>= 1) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      a[i] += __shfl_xor(a[i], off, 64);
+      b[i] += __shfl_xor(b[i], off, 64);
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane < p.c8s) {
+    float* row = lw + wave * 2 * Cs + lane * 8;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      row[i] = a[i];
+      row[Cs + i] = b[i];
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 2 * Cs) {
+    float v = 0.0f;
+    const int nw = (int)nthr >> 6;
+    for (int w = 0; w < nw; ++w) v += lw[w * 2 * Cs + t];
+    const int half = t >= Cs, j = t - half * Cs;
+    partial[(long long)blockIdx.x * 2 * C + half * C + blockIdx.y * Cs + j] = v;
+  }
+}
+
+// LDS of slab_fold: 16 waves x 2*64 sums
+constexpr int kSlabLds = 16 * 2 * 64;
+
 // ---------------- forward ----------------
 
-// K1: per-channel sum and sum-of-squares PARTIALS (training stats).
+template <bool MASKED>
+__device__ __forceinline__ void stats_round4(const bf16* __restrict__ x,
+                                             const long long r,
+                                             const long long rstride,
+                                             const long long M, const int C,
+                                             const int c0, float (&s)[8],
+                                             float (&q)[8]) {
+  const Round4<MASKED> rd(r, rstride, M);
+  F8 v[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) v[u] = load8(x + rd.row[u] * C + c0);
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const float e = rd.ok[u] ? v[u].v[i] : 0.0f;
+      s[i] += e;
+      q[i] = fmaf(e, e, q[i]);
+    }
+  }
+}
+
+// K1s: bn_stats on the slab partition.
+__global__ __launch_bounds__(1024) void bn_stats_slab_kernel(
+    const bf16* __restrict__ x, float* __restrict__ partial,  // [R, 2C]
+    const long long M, const int C) {
+  __shared__ float lw[kSlabLds];
+  const SlabPart p = slab_partition(C, blockDim.x);
+  float s[8] = {0}, q[8] = {0};
+  long long r = p.row0;
+  for (; r + 3 * p.rstride < M; r += 4 * p.rstride)
+    stats_round4<false>(x, r, p.rstride, M, C, p.c0, s, q);
+  if (r < M) stats_round4<true>(x, r, p.rstride, M, C, p.c0, s, q);
+  slab_fold(lw, s, q, p, C, blockDim.x, partial);
+}
+
+// K1: per-channel sum and sum-of-squares PARTIALS (training stats), row-only
+// partition (EDL_BN_SLAB=0).
 __global__ void bn_stats_kernel(
     const bf16* __restrict__ x, float* __restrict__ partial,  // [grid, 2C]
     const long long M, const int C) {
@@ -310,7 +439,68 @@ __device__ __forceinline__ void bwd_reduce_rows(
   }
 }
 
-// B1: per-channel PARTIALS of s1 = sum(dy_eff), s2 = sum(dy_eff * xhat).
+// One 4-row round of the backward reduce on the slab partition, as two
+// 2-row batches like the row-only loop above. A masked-out row selects
+// nothing through the ReLU select (mask byte 0).
+template <bool RELU, bool MASKED>
+__device__ __forceinline__ void bwd_round4(
+    const bf16* __restrict__ dy, const unsigned char* __restrict__ mask,
+    const bf16* __restrict__ x, const long long r, const long long rstride,
+    const long long M, const int C, const int c0, const float (&mu)[8],
+    const float (&is)[8], float (&s1)[8], float (&s2)[8]) {
+  const Round4<MASKED> rd(r, rstride, M);
+  const int c8 = C >> 3, oct = c0 >> 3;
+#pragma unroll
+  for (int u = 0; u < 4; u += 2) {
+    const long long e0 = rd.row[u] * C + c0, e1 = rd.row[u + 1] * C + c0;
+    F8 g0 = load8(dy + e0), g1 = load8(dy + e1);
+    F8 x0 = load8(x + e0), x1 = load8(x + e1);
+    if (RELU || MASKED) {
+      unsigned m0 = 0xffu, m1 = 0xffu;
+      if (RELU) {
+        m0 = mask[rd.row[u] * c8 + oct];
+        m1 = mask[rd.row[u + 1] * c8 + oct];
+      }
+      relu_select(g0, rd.ok[u] ? m0 : 0u);
+      relu_select(g1, rd.ok[u + 1] ? m1 : 0u);
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      s1[i] += g0.v[i] + g1.v[i];
+      s2[i] = fmaf(g0.v[i], (x0.v[i] - mu[i]) * is[i],
+                   fmaf(g1.v[i], (x1.v[i] - mu[i]) * is[i], s2[i]));
+    }
+  }
+}
+
+// B1s: bn_bwd_reduce on the slab partition.
+template <bool RELU>
+__global__ __launch_bounds__(1024) void bn_bwd_reduce_slab_kernel(
+    const bf16* __restrict__ dy, const unsigned char* __restrict__ mask,
+    const bf16* __restrict__ x, const float* __restrict__ mean,
+    const float* __restrict__ invstd, float* __restrict__ partial,  // [R, 2C]
+    const long long M, const int C) {
+  __shared__ float lw[kSlabLds];
+  const SlabPart p = slab_partition(C, blockDim.x);
+  float mu[8], is[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    mu[i] = mean[p.c0 + i];
+    is[i] = invstd[p.c0 + i];
+  }
+  float s1[8] = {0}, s2[8] = {0};
+  long long r = p.row0;
+  for (; r + 3 * p.rstride < M; r += 4 * p.rstride)
+    bwd_round4<RELU, false>(dy, mask, x, r, p.rstride, M, C, p.c0, mu, is, s1,
+                            s2);
+  if (r < M)
+    bwd_round4<RELU, true>(dy, mask, x, r, p.rstride, M, C, p.c0, mu, is, s1,
+                           s2);
+  slab_fold(lw, s1, s2, p, C, blockDim.x, partial);
+}
+
+// B1: per-channel PARTIALS of s1 = sum(dy_eff), s2 = sum(dy_eff * xhat),
+// row-only partition (EDL_BN_SLAB=0 and the fused kernel).
 template <bool RELU>
 __global__ void bn_bwd_reduce_kernel(
     const bf16* __restrict__ dy, const unsigned char* __restrict__ mask,
@@ -559,31 +749,63 @@ static int bn_grid_common(long long M, int C, long long cap_env) {
   return (int)(g > 0 ? g : 1);
 }
 
-extern "C" int bn_stats_grid(long long M, int C) {
-  // cover the tensor with enough blocks for bandwidth, but keep the
-  // partial buffer (grid x 2C fp32) around <= 1 MiB.
-  // The fwd finalize (bn_finalize.hip) reads up to 192 rows in one batch
-  // of loads, so its cost no longer grows with the grid up to there; the
-  // bwd finalize still walks its rows 8 at a time (~4.7 us up to 192 rows,
-  // the dispatch floor). EDL_BN_GRID_CAP overrides for A/B; 192 stays:
-  // the bwd sweep still loses at 384 and 768
-  // (profiles/bn_finalize_trace_before_after.txt).
-  return bn_grid_common(M, C, env_ll("EDL_BN_GRID_CAP", 192));
+// Row-block bound of the slab plan: R * S <= kSlabBlocks keeps a wide layer
+// at 4096 waves of 256-thread blocks, four per SIMD of a 256-CU part, all
+// resident at once.
+constexpr int kSlabBlocks = 1024;
+constexpr int kSlabWaves = 4096;
+
+extern "C" BnReducePlan bn_reduce_plan(long long M, int C, int backward,
+                                       int slab) {
+  // R, the partial row count, stays <= 192 either way: the fwd finalize
+  // (bn_finalize.hip) reads up to 192 rows in one batch of loads, so its
+  // cost does not grow with R up to there; the bwd finalize walks its rows
+  // 8 at a time (~4.7 us up to 192 rows, the dispatch floor) and loses
+  // above (profiles/bn_finalize_trace_before_after.txt: 384 and 768).
+  // EDL_BN_GRID_CAP / EDL_BN_BWD_GRID_CAP override the 192 for A/B.
+  long long cap_env = env_ll("EDL_BN_GRID_CAP", 192);
+  if (backward) cap_env = env_ll("EDL_BN_BWD_GRID_CAP", cap_env);
+  BnReducePlan p;
+  p.slab = slab;
+  if (!slab) {
+    // row-only partition: a block covers all C channels; the partial
+    // buffer (grid x 2C fp32) is held to 512 KiB
+    p.R = bn_grid_common(M, C, cap_env);
+    p.S = 1;
+    p.Cs = C;
+    p.nthr = 256;
+    return p;
+  }
+  p.Cs = C < 64 ? C : 64;
+  p.S = C / p.Cs;
+  const int c8s = p.Cs >> 3;
+  long long rcap = kSlabBlocks / p.S;
+  if (rcap > cap_env) rcap = cap_env;
+  if (rcap < 1) rcap = 1;
+  for (p.nthr = 256;; p.nthr *= 2) {
+    // one 4-row round per thread until R reaches its cap
+    const long long rpb = p.nthr / c8s;
+    long long r = (M + 4 * rpb - 1) / (4 * rpb);
+    p.R = (int)(r < 1 ? 1 : r > rcap ? rcap : r);
+    // more than two rounds a thread (C <= 256 at large M, where R is
+    // capped and slabs cannot help): a larger block, while the grid stays
+    // within kSlabWaves
+    if (p.nthr == 1024 || M <= 8 * p.R * rpb ||
+        (long long)p.R * p.S * (2 * p.nthr / 64) > kSlabWaves)
+      break;
+  }
+  return p;
 }
 
-extern "C" int bn_bwd_grid(long long M, int C) {
-  // the BWD reduce grid is decoupled from the fwd one: with the
-  // strip-parallel finalize the partial-read cost no longer binds the
-  // grid, so the reduce can run wider for bandwidth.
-  return bn_grid_common(M, C,
-                        env_ll("EDL_BN_BWD_GRID_CAP",
-                               env_ll("EDL_BN_GRID_CAP", 192)));
-}
-
-extern "C" void launch_bn_stats(const void* x, float* partial, int grid,
-                                long long M, int C, hipStream_t s) {
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(grid), dim3(256), 0, s,
-                     (const bf16*)x, partial, M, C);
+extern "C" void launch_bn_stats(const void* x, float* partial,
+                                BnReducePlan plan, long long M, int C,
+                                hipStream_t s) {
+  if (plan.slab)
+    hipLaunchKernelGGL(bn_stats_slab_kernel, dim3(plan.R, plan.S),
+                       dim3(plan.nthr), 0, s, (const bf16*)x, partial, M, C);
+  else
+    hipLaunchKernelGGL(bn_stats_kernel, dim3(plan.R), dim3(256), 0, s,
+                       (const bf16*)x, partial, M, C);
 }
 
 extern "C" void launch_bn_bwd_finalize(const float* partial, int nblocks,
@@ -617,14 +839,22 @@ extern "C" void launch_bn_apply(const void* x, const void* res, void* y,
 extern "C" void launch_bn_bwd_reduce(const void* dy, const unsigned char* mask,
                                      const void* x,
                                      const float* mean, const float* invstd,
-                                     float* partial, int grid, long long M, int C,
-                                     bool relu, hipStream_t s) {
+                                     float* partial, BnReducePlan plan,
+                                     long long M, int C, bool relu,
+                                     hipStream_t s) {
   dispatch_bools(
       [&](auto R) {
         constexpr bool RELU = decltype(R)::value;
-        hipLaunchKernelGGL((bn_bwd_reduce_kernel<RELU>), dim3(grid), dim3(256),
-                           0, s, (const bf16*)dy, RELU ? mask : nullptr,
-                           (const bf16*)x, mean, invstd, partial, M, C);
+        if (plan.slab)
+          hipLaunchKernelGGL((bn_bwd_reduce_slab_kernel<RELU>),
+                             dim3(plan.R, plan.S), dim3(plan.nthr), 0, s,
+                             (const bf16*)dy, RELU ? mask : nullptr,
+                             (const bf16*)x, mean, invstd, partial, M, C);
+        else
+          hipLaunchKernelGGL((bn_bwd_reduce_kernel<RELU>), dim3(plan.R),
+                             dim3(256), 0, s, (const bf16*)dy,
+                             RELU ? mask : nullptr, (const bf16*)x, mean,
+                             invstd, partial, M, C);
       },
       relu);
 }

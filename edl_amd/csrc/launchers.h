@@ -127,10 +127,15 @@ void launch_softmax_ce_bwd(const void* s, int is_bf16, const float* lse,
 
 // ---- bnrelu.hip ---- (M is long long, C int; the accumulators go
 // db_acc THEN dg_acc; the *_pad launchers take Nimg, H, W, C as ints)
-int bn_stats_grid(long long M, int C);
-int bn_bwd_grid(long long M, int C);
-void launch_bn_stats(const void* x, float* partial, int grid, long long M,
-                     int C, hipStream_t s);
+// The partition of bn_stats / bn_bwd_reduce: grid (R row-blocks, S channel
+// slabs of Cs channels), nthr threads a block, partial [R, 2C] fp32.
+// slab == 0 is the row-only partition (S = 1, Cs = C, 256 threads).
+struct BnReducePlan {
+  int slab, R, S, Cs, nthr;
+};
+BnReducePlan bn_reduce_plan(long long M, int C, int backward, int slab);
+void launch_bn_stats(const void* x, float* partial, BnReducePlan plan,
+                     long long M, int C, hipStream_t s);
 void launch_bn_finalize(float* partial, int nblocks, int zero_src,
                         const float* gamma, const float* beta, float* mean,
                         float* invstd, float* scale, float* shift,
@@ -145,8 +150,9 @@ void launch_bn_apply_pad(const void* x, void* yp, unsigned char* mask,
                          int H, int W, int C, hipStream_t s);
 void launch_bn_bwd_reduce(const void* dy, const unsigned char* mask,
                           const void* x, const float* mean,
-                          const float* invstd, float* partial, int grid,
-                          long long M, int C, bool relu, hipStream_t s);
+                          const float* invstd, float* partial,
+                          BnReducePlan plan, long long M, int C, bool relu,
+                          hipStream_t s);
 void launch_bn_bwd_finalize(const float* partial, int nblocks, float* sums,
                             int C, float* db_acc, float* dg_acc,
                             hipStream_t s);

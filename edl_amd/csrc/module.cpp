@@ -803,6 +803,13 @@ void check_bn_inputs(const torch::Tensor& x, int64_t C) {
               "rows; got ", C);
 }
 
+// EDL_BN_SLAB (default 1): 0 runs bn_stats / bn_bwd_reduce on the row-only
+// partition. Read per call (not static) so tests can A/B via os.environ.
+static int bn_slab_enabled() {
+  const char* e = getenv("EDL_BN_SLAB");
+  return e ? atoi(e) != 0 : 1;
+}
+
 std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
                                         torch::Tensor beta, torch::Tensor rmean,
                                         torch::Tensor rvar, double momentum,
@@ -826,7 +833,8 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
     pad = parse_pad_hw(*pad_hw, M, "bn");
   }
   auto opts = gamma.options().dtype(torch::kFloat32);
-  const int grid = bn_stats_grid(M, (int)C);
+  const BnReducePlan plan = bn_reduce_plan(M, (int)C, 0, bn_slab_enabled());
+  const int grid = plan.R;
   auto partial = torch::empty({grid, 2 * C}, opts);
   auto mean = torch::empty({C}, opts);
   auto invstd = torch::empty({C}, opts);
@@ -850,7 +858,7 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
     partial = *pre_part;
     fin_grid = (int)pre_part->size(0);
   } else {
-    launch_bn_stats(x.data_ptr(), partial.data_ptr<float>(), grid, M, (int)C,
+    launch_bn_stats(x.data_ptr(), partial.data_ptr<float>(), plan, M, (int)C,
                     s);
   }
   // zero-after-read ONLY for pooled buffers (capped partials): transient
@@ -910,11 +918,14 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
   check_bn_inputs(x, C);
   const long long M = x.numel() / C;
   auto opts = gamma.options().dtype(torch::kFloat32);
-  const int grid = bn_bwd_grid(M, (int)C);
   auto sums = torch::empty({2, C}, opts);
   // read per call (not static) so tests can A/B via os.environ
   const char* fenv = getenv("EDL_BN_BWD_FUSED");
   const bool fused_bwd = fenv ? atoi(fenv) != 0 : false;
+  // the single-launch kernel reduces on the row-only partition
+  const BnReducePlan plan = bn_reduce_plan(
+      M, (int)C, 1, bn_slab_enabled() && !(fused_bwd && training));
+  const int grid = plan.R;
   PadNHW pad;  // pad.n == 0: plain [M, C] dx
   if (pad_hw.has_value() && !(fused_bwd && training)) {
     TORCH_CHECK(training && !add, "bn_bwd: pad_hw needs training, no residual");
@@ -967,7 +978,7 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
   auto partial = torch::empty({grid, 2 * C}, opts);
   launch_bn_bwd_reduce(dyc.data_ptr(), mp, x.data_ptr(),
                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
-                       partial.data_ptr<float>(), grid, M, (int)C, relu, s);
+                       partial.data_ptr<float>(), plan, M, (int)C, relu, s);
   launch_bn_bwd_finalize(partial.data_ptr<float>(), grid, sums.data_ptr<float>(),
                          (int)C, db_acc, dg_acc, s);
   if (pad.n) {
