@@ -788,7 +788,7 @@ void check_bn_inputs_eval(const torch::Tensor& x, int64_t C) {
   // stage-4 BNs are 4096-wide)
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16,
               "bn: bf16 GPU tensor required");
-  TORCH_CHECK(C % 8 == 0, "bn: C % 8 == 0 required, got ", C);
+  TORCH_CHECK(C > 0 && C % 8 == 0, "bn: C % 8 == 0 required, got ", C);
 }
 
 void check_bn_inputs(const torch::Tensor& x, int64_t C) {
@@ -801,6 +801,60 @@ void check_bn_inputs(const torch::Tensor& x, int64_t C) {
               "bn: training needs a power-of-two C (8..2048): the stats and "
               "reduce kernels split each 256-thread block into C/8-thread "
               "rows; got ", C);
+}
+
+// Operand checks of bn_fwd_train, bn_fwd_eval and bn_bwd. The bnrelu.hip
+// kernels index every operand by (row, channel octet) without a bounds test,
+// so, like bn_wide_* below, the bindings check every pointer they pass on
+// for dtype, size, layout and device. C is the numel of the first
+// per-channel tensor (gamma, or scale in eval); `training` adds the width
+// limits of the stats/reduce kernels. vecs: the per-channel tensors, fp32
+// [C] each (an undefined one, e.g. no running stats, is skipped). res: the
+// residual, x's shape. dy: the incoming gradient, x's shape; it may be
+// non-contiguous, the binding copies it. mask: the fwd ReLU mask, checked
+// when the caller passes a pointer to it (the relu path), ignored otherwise.
+struct BnVec {
+  const char* name;
+  const torch::Tensor& t;
+};
+
+static void check_bn_operands(
+    const char* who, const torch::Tensor& x, int64_t C, bool training,
+    std::initializer_list<BnVec> vecs,
+    const c10::optional<torch::Tensor>& res, const torch::Tensor* dy = nullptr,
+    const c10::optional<torch::Tensor>* mask = nullptr) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kBFloat16,
+              "bn: bf16 GPU tensor required");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == C && x.is_contiguous(),
+              "bn: x must be a contiguous [M, C] view");
+  if (training)
+    check_bn_inputs(x, C);
+  else
+    check_bn_inputs_eval(x, C);
+  for (const BnVec& v : vecs) {
+    if (!v.t.defined()) continue;
+    TORCH_CHECK(v.t.device() == x.device() &&
+                    v.t.scalar_type() == torch::kFloat32 && v.t.dim() == 1 &&
+                    v.t.size(0) == C && v.t.is_contiguous(),
+                who, ": ", v.name, " must be fp32 [C], contiguous, on x's GPU");
+  }
+  if (res.has_value())
+    TORCH_CHECK(res->device() == x.device() &&
+                    res->scalar_type() == torch::kBFloat16 &&
+                    res->sizes() == x.sizes() && res->is_contiguous(),
+                who, ": res must be bf16 [M, C], contiguous, on x's GPU");
+  if (dy != nullptr)
+    TORCH_CHECK(dy->device() == x.device() &&
+                    dy->scalar_type() == torch::kBFloat16 &&
+                    dy->sizes() == x.sizes(),
+                who, ": dy must be bf16 [M, C] on x's GPU");
+  if (mask != nullptr)
+    TORCH_CHECK(mask->has_value() && (*mask)->device() == x.device() &&
+                    (*mask)->scalar_type() == torch::kUInt8 &&
+                    (*mask)->numel() == x.size(0) * (C / 8) &&
+                    (*mask)->is_contiguous(),
+                who, ": relu path needs the fwd mask, uint8 [M, C/8] on x's "
+                "GPU");
 }
 
 // EDL_BN_SLAB (default 1): 0 runs bn_stats / bn_bwd_reduce on the row-only
@@ -822,10 +876,13 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
   // pad_hw = (H, W): y is returned as the zero-halo padded buffer
   // [N, H+2, W+2, C] the 3x3 implicit-GEMM kernels read (relu, no res).
   const int64_t C = gamma.numel();
-  TORCH_CHECK(x.dim() == 2 && x.size(1) == C && x.is_contiguous(),
-              "bn: x must be a contiguous [M, C] view");
-  check_bn_inputs(x, C);
-  const long long M = x.numel() / C;
+  check_bn_operands("bn_fwd_train", x, C, true,
+                    {{"gamma", gamma}, {"beta", beta}, {"running_mean", rmean},
+                     {"running_var", rvar}},
+                    res);
+  TORCH_CHECK(rmean.defined() == rvar.defined(),
+              "bn_fwd_train: running_mean and running_var come together");
+  const long long M = x.size(0);
   PadNHW pad;  // pad.n == 0: plain [M, C] output
   if (pad_hw.has_value()) {
     TORCH_CHECK(relu && !res.has_value(),
@@ -892,8 +949,9 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor gamma,
 torch::Tensor bn_fwd_eval(torch::Tensor x, torch::Tensor scale, torch::Tensor shift,
                           c10::optional<torch::Tensor> res, bool relu) {
   const int64_t C = scale.numel();
-  check_bn_inputs_eval(x, C);
-  const long long M = x.numel() / C;
+  check_bn_operands("bn_fwd_eval", x, C, false,
+                    {{"scale", scale}, {"shift", shift}}, res);
+  const long long M = x.size(0);
   auto y = torch::empty_like(x);
   launch_bn_apply(x.data_ptr(), res.has_value() ? res->data_ptr() : nullptr,
                   y.data_ptr(), nullptr,
@@ -915,8 +973,10 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
   // single-launch EDL_BN_BWD_FUSED route returns the plain [M, C] dx and
   // the caller tells the two apart by dx.dim()).
   const int64_t C = gamma.numel();
-  check_bn_inputs(x, C);
-  const long long M = x.numel() / C;
+  check_bn_operands("bn_bwd", x, C, true,
+                    {{"gamma", gamma}, {"mean", mean}, {"invstd", invstd}},
+                    c10::nullopt, &dy, relu ? &msk : nullptr);
+  const long long M = x.size(0);
   auto opts = gamma.options().dtype(torch::kFloat32);
   auto sums = torch::empty({2, C}, opts);
   // read per call (not static) so tests can A/B via os.environ
@@ -936,8 +996,6 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor dy, c10::optional<torch::Tensor>
   auto dres = add ? torch::empty_like(x) : torch::Tensor();
   auto s = cur_stream();
   auto dyc = dy.is_contiguous() ? dy : dy.contiguous();
-  TORCH_CHECK(!relu || (msk.has_value() && msk->numel() == M * (C / 8)),
-              "bn_bwd: relu path needs the fwd mask");
   const unsigned char* mp =
       relu ? (const unsigned char*)msk->data_ptr() : nullptr;
   // direct-grad mode: accumulate dgamma/dbeta straight into the params'
